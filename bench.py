@@ -14,7 +14,14 @@ One step = one epoch exactly as the reference's `_sgd` runs it
 plus the training-RMSE pass.  value = ratings * steps / wall time of the
 timed steps (inputs resident in HBM, max over ranks).
 
-Also reported (rank 0):
+A plain run sets up, warms up, times the steps and prints the line (dtype
+auto = the FP64 headline alone).  --dump-outputs DIR then writes what the
+last timed step left (dump_outputs()).  --full adds, as before it existed:
+the CPU baseline and parity leg, the FP32 perf layout nested as
+`fp32_layout`, and at N > 1 the nested delta-exchange leg and the
+post-timing self-checks (`multi_gpu`).
+
+Also reported (rank 0; cpu_baseline and parity with --full only):
   roofline      SGD-kernel algorithmic HBM bytes / SGD-phase time (one
                 hipEvent pair around each timed epoch's launches) against
                 8 TB/s.  Algorithmic bytes: SURVEY 8(d)'s 16k+28 B per update
@@ -131,6 +138,35 @@ def synth(n_users: int, n_items: int, nnz: int, seed: int = 20261015):
     return u, i, r
 
 
+DUMP_SEED = 20261019
+DUMP_ARRAY_BYTES = 16 << 20     # per array; no workload writes more than four large ones
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: ``arrays`` (name -> device tensor, host array or list;
+    the state the last timed step left) as ``dirname/<name>.npy``, float32
+    where the array is float32, else float64.  An array above
+    DUMP_ARRAY_BYTES is cut to a sample of its rows, drawn without
+    replacement by RandomState(DUMP_SEED) and kept in row order: a function
+    of the array's shape alone, so two builds write the same rows."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        row_bytes = max(a[0].numel(), 1) * (4 if a.dtype == torch.float32 else 8)
+        keep = DUMP_ARRAY_BYTES // row_bytes
+        if a.shape[0] > keep:
+            rows = np.sort(np.random.RandomState(DUMP_SEED).choice(a.shape[0], keep,
+                                                                   replace=False))
+            a = a.index_select(0, torch.from_numpy(rows).to(a.device))
+        a = a.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+    log(f"outputs ({', '.join(arrays)}) written to {dirname}")
+
+
 def traffic_from_profiles(workload: str, n_gpus: int, schedule: str, dtype: str,
                           kernel: str, emulate: int = 0):
     """HBM bytes per SGD launch measured by rocprofv3 PMC passes for exactly
@@ -245,6 +281,9 @@ def run_als(args, u, i, r, nu, ni, nnz, k, desc, mu, P0, Q0, dev) -> int:
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     rmse = eng.rmse_values(args.warmup + args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"P": eng.P, "Q": eng.Q, "bu": eng.bu, "bi": eng.bi,
+                                         "rmse_per_epoch": rmse})
     roofline = phases = None
     if events:
         us = sum(e[0].elapsed_time(e[1]) for e in events) / 1e3
@@ -347,7 +386,9 @@ def run_topk(args, u, i, r, nu, ni, nnz, k, desc, mu, P0, Q0, dev) -> int:
     elapsed = time.perf_counter() - t0
     mm = bool(batch["mm"])
     fallback = eng.topk_finish(batch)      # an overflowed filter re-runs exactly (untimed)
-    if mm:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"items": batch["items"], "scores": batch["scores"]})
+    if mm and args.full:
         # the whole batch against the exact kernels (untimed): same ids, same scores
         got_i, got_s = batch["items"].clone(), batch["scores"].clone()
         eng.topk_launch(batch, exact=True)
@@ -774,16 +815,27 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the CPU baseline and parity leg "
+                         "(--cpu-sample), with --dtype auto the FP32 perf layout nested as "
+                         "`fp32_layout`, at N > 1 the nested delta-exchange leg and the "
+                         "post-timing checks (`multi_gpu`); top-k: the MFMA filter against the "
+                         "exact kernels.  Minutes of host time at the default workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left (SGD / ALS: "
+                         "P, Q, bu, bi, rmse_per_epoch; top-k: items, scores; rank 0's at "
+                         "N > 1) as DIR/<name>.npy (dump_outputs: large arrays as a fixed "
+                         "seeded sample of rows)")
     ap.add_argument("--dtype", default="auto", choices=["auto", "float32", "float64"],
                     help="SGD workloads: auto (default) = the reference's FP64 arithmetic "
-                         "as the headline line, the FP32 perf layout measured in the same "
-                         "run and nested as `fp32_layout`; ALS / top-k: auto = float32")
+                         "as the headline line, with --full the FP32 perf layout measured in "
+                         "the same run and nested as `fp32_layout`; ALS / top-k: auto = float32")
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--reg", type=float, default=None,
                     help="default 0.02 for SGD (project_template/pipeline/train.py:29-36), "
                          "1.0 for ALS (KernelMF's default reg)")
-    ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="CPU leg: -1 = one full epoch (default; parity in the strata "
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="--full's CPU leg: -1 = one full epoch (default; parity in the strata "
                          "order and in the reference's shuffle order), N > 0 = the first "
                          "strata of epoch 1 covering >= N ratings, 0 = skip")
     ap.add_argument("--no-phase-timing", action="store_true",
@@ -801,7 +853,7 @@ def main() -> int:
                          "between N sub-epochs (exact: a sequential order, DESIGN.md 6); "
                          "delta = item deltas all-reduced once per epoch, applied damped")
     ap.add_argument("--no-delta-leg", action="store_true",
-                    help="N > 1, --exchange rotate: skip the nested delta-exchange run")
+                    help="--full, N > 1, --exchange rotate: skip the nested delta-exchange run")
     ap.add_argument("--relabel", type=int, default=None,
                     help="N > 1, --exchange rotate: item relabellings, one drawn per epoch "
                          "(default distributed.ROTATE_RELABEL = 8; 1 = the plain rotation)")
@@ -820,8 +872,8 @@ def main() -> int:
                          "launch stream after every epoch (default: on a side stream beside "
                          "the next epoch's sub-epochs)")
     ap.add_argument("--no-check", action="store_true",
-                    help="N > 1: skip the post-timing checks (replica checksums on every "
-                         "rank, rank 0's one-GPU replay of the same order, the N=1 RMSE leg)")
+                    help="--full, N > 1: skip rank 0's part of the post-timing checks (its "
+                         "one-GPU replay of the same order, the N=1 RMSE leg)")
     ap.add_argument("--rmse-overlap", action="store_true",
                     help="one GPU: run each epoch's RMSE pass on a side stream from a "
                          "parameter snapshot, beside the next epoch's sweep")
@@ -829,6 +881,10 @@ def main() -> int:
                     help="N>1 process group: nccl (= RCCL, one GPU per rank) or gloo "
                          "(rehearsal: ranks may share a GPU, LOCAL_RANK mod device count)")
     args = ap.parse_args()
+    if args.cpu_sample is None:
+        args.cpu_sample = -1 if args.full else 0
+    elif args.cpu_sample != 0 and not args.full:
+        ap.error("--cpu-sample: the CPU leg runs with --full only")
     record_maps_at_exit()
     if args.relabel is None:
         from matrix_factorization.distributed import ROTATE_RELABEL
@@ -878,7 +934,8 @@ def main() -> int:
         return run_topk(args, u, i, r, nu, ni, nnz, k, desc, mu, P0, Q0, dev)
     if args.reg is None:
         args.reg = 0.02
-    dtypes = ["float64", "float32"] if args.dtype == "auto" else [args.dtype]
+    dtypes = [args.dtype] if args.dtype != "auto" else \
+        ["float64", "float32"] if args.full else ["float64"]
     shared = {}
     outs = []
     for dt in dtypes:
@@ -886,11 +943,13 @@ def main() -> int:
         outs.append(run_sgd(args, dt, world, rank, dev, u, i, r, nu, ni, nnz, k, kernel, desc,
                             mu, P0, Q0, shared))
         torch.cuda.empty_cache()
+        # --dump-outputs: the headline run's; the nested legs write nothing
+        args = argparse.Namespace(**{**vars(args), "dump_outputs": None})
     # N > 1, rotate: the other exchange measured in the same job and nested
     # (`delta_exchange`), so one N-GPU run maps both ends of the frontier
     # (exact order vs damped item deltas)
     delta_leg = None
-    if (world > 1 and args.exchange == "rotate" and args.schedule == "strata"
+    if (args.full and world > 1 and args.exchange == "rotate" and args.schedule == "strata"
             and not args.no_delta_leg):
         log(f"---- {dtypes[0]} run, exchange delta (nested leg)")
         da = argparse.Namespace(**{**vars(args), "exchange": "delta"})
@@ -1172,8 +1231,11 @@ def run_sgd(args, dtype, world, rank, dev, u, i, r, nu, ni, nnz, k, kernel, desc
     if rot is not None:       # the live canonical replica whole again (checks), SSEs landed
         rot.finish(n_ep - 1)
     rmse = global_rmse(eng, n_ep, nnz)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"P": eng.P, "Q": eng.Q, "bu": eng.bu, "bi": eng.bi,
+                                         "rmse_per_epoch": rmse})
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         multi = multi_checks(args, eng, rotate, world, rank, dev, u, i, r, nu, ni, k, kernel, mu,
                              P0, Q0, n_ep, rmse)
 

@@ -1,4 +1,4 @@
-"""The N > 1 bench line, end to end: bench.py under torch.distributed.run
+"""The N > 1 bench line, end to end: bench.py --full under torch.distributed.run
 with two gloo ranks sharing cuda:0 (the driver's 8-GPU runs use nccl, one
 GPU per rank; the code path after init is the same).  The line must carry
 the self-checks of DESIGN.md section 6.5: every rank's [Q | b_i] replica
@@ -32,7 +32,7 @@ def test_bench_two_ranks_checks_itself(exchange):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus",
            "2", "--backend", "gloo", "--workload", "small", "--steps", "2", "--warmup", "1",
-           "--exchange", exchange]
+           "--exchange", exchange, "--full"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=540)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [x for x in out.stdout.splitlines() if x.startswith("{")]
@@ -75,7 +75,7 @@ def test_bench_c4_shape_eight_ranks_rotate():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus",
            "8", "--backend", "gloo", "--workload", "c3", "--steps", "1", "--warmup", "1",
-           "--dtype", "float64"]
+           "--dtype", "float64", "--full"]
     env = dict(os.environ, MF_STRATA_PERSISTENT="0")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=540, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -10,7 +10,8 @@
 #
 #   test[:PATH]          pytest -m gpu (all of tests/, or PATH)
 #   smoke                __graft_entry__.smoke()
-#   bench[:ARGS]         python bench.py ARGS            (stdout = the JSON line)
+#   bench[:ARGS]         python bench.py ARGS            (stdout = the JSON line; --full
+#                        in ARGS for cpu_baseline, parity, fp32_layout, multi_gpu)
 #   trace[:ARGS]         rocprofv3 --kernel-trace --stats -- python bench.py ARGS
 #   pmc:CTRS[:ARGS]      rocprofv3 --pmc CTRS (+ kernel trace) -- python bench.py ARGS
 #                        (CTRS '+'-separated; one pass, within the per-block limits)

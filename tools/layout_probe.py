@@ -33,7 +33,7 @@ def first_appearance(x, n):
 def main():
     if "--after-bench" in sys.argv:        # bench.py's own run first, in this process
         argv = sys.argv
-        sys.argv = ["bench.py", "--cpu-sample", "0", "--steps", "5"]
+        sys.argv = ["bench.py", "--full", "--cpu-sample", "0", "--steps", "5"]
         bench.main()
         sys.argv = argv
     import torch
