@@ -481,6 +481,53 @@ int mf_als_sweep_probe(const int64_t* entity_ptr, const int32_t* other_ids,
                        void* biases, void* features, int32_t n_factors, int32_t dtype,
                        double reg, void* stream, int64_t* probe);
 
+/* ---------------- implicit-feedback ALS ---------------------------------- */
+
+/*
+ * Confidence-weighted ALS over ALL entity x other pairs (Hu, Koren & Volinsky
+ * 2008; no reference counterpart).  An observation n of entity e has strength
+ * r_n >= 0, confidence 1 + alpha r_n and preference [r_n > 0]; every pair
+ * that is not observed has confidence 1 and preference 0.  No biases, no
+ * global mean.  One half-sweep solves, for every entity e,
+ *     (G + sum_n alpha r_n z_n z_n^T + reg I) x_e = sum_{n: r_n > 0} (1 + alpha r_n) z_n,
+ *     z_n = other_features[o_n],  G = other_features^T other_features (all rows)
+ * with the sums over e's observed list.
+ *
+ * mf_gramian: gram = features^T features, (k, k) row-major float, both
+ * triangles, of a row-major (n_rows, k) matrix.  f32-input MFMA
+ * (v_mfma_f32_32x32x2_f32) per slab of rows, the slabs summed in a fixed order
+ * in FP64: no atomics, the same input gives the same bits.  n_rows == 0 writes
+ * zeros.
+ *   features        DEVICE, float, (n_rows, k)
+ *   workspace       DEVICE, mf_gramian_workspace_bytes(n_rows, k) bytes
+ *                   (0 for n_rows == 0 or an invalid n_factors)
+ *   gram            DEVICE, float, k * k, written
+ *
+ * mf_ials_sweep: one half-sweep.
+ *   entity_ptr      DEVICE, n_entities + 1 (int64): CSR offsets
+ *   other_ids       DEVICE, the other side's id per observation, CSR order
+ *   strengths       DEVICE, float, CSR order, >= 0
+ *   other_features  DEVICE, float, (n_other, k)
+ *   gram            DEVICE, float, k * k: mf_gramian(other_features)
+ *   features        DEVICE, float, written: (n_entities, k)
+ * Entities with an empty list keep their row (update_users re-solves only the
+ * users present in its data); an entity whose strengths are all 0 gets the
+ * zero vector.  The weighted Gramian runs on f32-input MFMA, the solve is an
+ * LDS elimination in f32 (the matrix is SPD: alpha >= 0, reg > 0).
+ *
+ * dtype must be MF_F32; 1 <= n_factors <= mf_als_max_factors(); alpha finite
+ * and >= 0; reg finite and > 0; counts >= 0 -- else MF_ERR_INVALID, before any
+ * device work, with the argument's name in mf_last_error().  n_entities == 0
+ * returns MF_OK.
+ */
+size_t mf_gramian_workspace_bytes(int64_t n_rows, int32_t n_factors);
+int mf_gramian(const void* features, int64_t n_rows, int32_t n_factors, int32_t dtype,
+               void* workspace, void* gram /* k*k, row-major */, void* stream);
+int mf_ials_sweep(const int64_t* entity_ptr, const int32_t* other_ids, const void* strengths,
+                  int32_t n_entities, const void* other_features, const void* gram,
+                  void* features, int32_t n_factors, int32_t dtype,
+                  double alpha, double reg, void* stream);
+
 /* ---------------- multi-GPU replica exchange ----------------------------- */
 
 /*

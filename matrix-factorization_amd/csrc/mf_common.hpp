@@ -207,5 +207,6 @@ void touch_strata_f64(hipStream_t s);
 void touch_bias(hipStream_t s);
 void touch_topk(hipStream_t s);
 void touch_als(hipStream_t s);
+void touch_ials(hipStream_t s);
 
 }  // namespace mf

@@ -302,6 +302,7 @@ extern "C" int mf_warmup(int32_t flags, void* stream) {
     touch_bias(s);
     touch_topk(s);
     touch_als(s);
+    touch_ials(s);
     lt.mark("warmup: other units");
     if (!(flags & MF_FLAG_NO_COOP)) {   // the cooperative launch path (persistent sweeps)
         void* no_args[1] = {nullptr};

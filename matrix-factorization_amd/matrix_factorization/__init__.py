@@ -7,13 +7,16 @@ BaselineModel train on the GPU through libmf_hip.so (hand-written gfx950
 kernels behind a C ABI, include/mf_hip.h); RecommenderBase and
 train_update_test_split are the host-side surface around them.  ALSMF (no
 reference counterpart: BASELINE config 5) fits the same linear factor model
-by alternating least squares with an MFMA Gramian.  The
+by alternating least squares with an MFMA Gramian; ImplicitALSMF (no
+reference counterpart either) fits implicit-feedback strengths by
+confidence-weighted ALS over all user x item pairs.  The
 neighbourhood and content-based models of the reference are outside this
 build's scope.
 """
 
 from .als_matrix_factorization import ALSMF
 from .baseline_model import BaselineModel
+from .implicit_als_matrix_factorization import ImplicitALSMF
 from .kernel_matrix_factorization import KernelMF
 from .recommender_base import RecommenderBase
 from .utils import train_update_test_split
@@ -21,6 +24,7 @@ from .utils import train_update_test_split
 __all__ = [
     "ALSMF",
     "BaselineModel",
+    "ImplicitALSMF",
     "KernelMF",
     "RecommenderBase",
     "train_update_test_split",

@@ -106,6 +106,10 @@ SIGNATURES = {
     "mf_als_max_factors": (ctypes.c_int32, []),
     "mf_als_sweep_probe": (ctypes.c_int, [
         _P, _P, _P, _I32, _F64, _P, _P, _P, _P, _I32, _I32, _F64, _P, _P]),
+    "mf_gramian_workspace_bytes": (ctypes.c_size_t, [_I64, _I32]),
+    "mf_gramian": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P]),
+    "mf_ials_sweep": (ctypes.c_int, [
+        _P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _F64, _F64, _P]),
     "mf_replica_delta": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P]),
     "mf_replica_apply": (ctypes.c_int, [_P, _P, _I64, _I32, _F64, _P]),
     "mf_warmup": (ctypes.c_int, [ctypes.c_int32, _P]),

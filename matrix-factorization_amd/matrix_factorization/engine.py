@@ -1916,6 +1916,85 @@ class FactorALS:
         self.sweep_items(reg)
 
 
+class ImplicitALS(FactorALS):
+    """Implicit-feedback ALS (Hu, Koren & Volinsky 2008; mf_gramian +
+    mf_ials_sweep) on FactorALS's CSR lists: the engine's ratings are
+    interaction strengths r >= 0 with confidence 1 + alpha r and preference
+    [r > 0]; every other pair counts with confidence 1 and preference 0.  The
+    engine must hold float32 linear-kernel parameters, global_mean 0 and zero
+    biases (they stay allocated and zero, so predict / topk score x_u . y_i)."""
+
+    def __init__(self, engine: SGDEngine):
+        super().__init__(engine)
+        e = engine
+        if e.global_mean != 0.0:
+            raise ValueError("implicit ALS has no global mean (engine.global_mean must be 0)")
+        if e.bu is None or e.bi is None or e.P is None or e.Q is None:
+            raise ValueError("implicit ALS needs the engine's parameters loaded")
+        if bool(torch.any(e.bu != 0)) or bool(torch.any(e.bi != 0)):
+            raise ValueError("implicit ALS has no biases (engine biases must be zero)")
+        lib = _lib.load()
+        ws = max(lib.mf_gramian_workspace_bytes(e.n_users, e.k),
+                 lib.mf_gramian_workspace_bytes(e.n_items, e.k), 4)
+        self.ws = torch.empty((ws + 3) // 4, dtype=torch.float32, device=e.dev)
+        self.gram = torch.empty((e.k, e.k), dtype=torch.float32, device=e.dev)
+        self.gram2 = torch.empty((e.k, e.k), dtype=torch.float32, device=e.dev)
+
+    def gramian(self, F: torch.Tensor, n: int, out: torch.Tensor) -> torch.Tensor:
+        """out = F^T F over the n rows of F (mf_gramian)."""
+        e = self.e
+        with torch.cuda.device(e.dev):
+            _lib.call("mf_gramian", _tp(F), n, e.k, e.dcode, _tp(self.ws), _tp(out), e.stream)
+        return out
+
+    def _isweep(self, csr, n, oq, n_other, q, alpha, reg):
+        e = self.e
+        ptr, oth, rr = csr
+        self.gramian(oq, n_other, self.gram)
+        with torch.cuda.device(e.dev):
+            _lib.call("mf_ials_sweep", _tp(ptr), _tp(oth), _tp(rr), n, _tp(oq), _tp(self.gram),
+                      _tp(q), e.k, e.dcode, float(alpha), float(reg), e.stream)
+
+    def sweep_users(self, alpha: float, reg: float) -> None:
+        """User rows from the current item side."""
+        e = self.e
+        self._isweep(self.user_csr, e.n_users, e.Q, e.n_items, e.P, alpha, reg)
+
+    def sweep_items(self, alpha: float, reg: float) -> None:
+        """Item rows from the current user side."""
+        e = self.e
+        self._isweep(self.item_csr, e.n_items, e.P, e.n_users, e.Q, alpha, reg)
+
+    def epoch(self, alpha: float, reg: float) -> None:
+        self.sweep_users(alpha, reg)
+        self.sweep_items(alpha, reg)
+
+    def loss_async(self, alpha: float, reg: float) -> torch.Tensor:
+        """The loss over all n_users x n_items pairs as a device scalar (FP64),
+        without a dense pass:
+            sum_obs [c (p - s)^2 - s^2] + <P^T P, Q^T Q>_F + reg (|P|_F^2 + |Q|_F^2),
+        s = p_u . q_i from mf_predict; the Frobenius term and the norms from
+        the two Gramians."""
+        e = self.e
+        with torch.cuda.device(e.dev):
+            obs = torch.zeros((), dtype=torch.float64, device=e.dev)
+            if e.n:
+                s = torch.empty(e.n, dtype=e.tdt, device=e.dev)
+                _lib.call("mf_predict", _tp(e.u), _tp(e.i), e.n, 0.0, _tp(e.bu), _tp(e.bi),
+                          _tp(e.P), _tp(e.Q), e.k, e.kcode, e.dcode, e.gamma, e.min_rating,
+                          e.max_rating, 0, _tp(s), e.stream)
+                s = s.double()
+                r = e.r.double()
+                d = (r > 0).double() - s
+                obs = torch.sum((1.0 + float(alpha) * r) * d * d - s * s)
+            gp = self.gramian(e.P, e.n_users, self.gram).double()
+            gq = self.gramian(e.Q, e.n_items, self.gram2).double()
+            return obs + torch.sum(gp * gq) + float(reg) * (torch.trace(gp) + torch.trace(gq))
+
+    def loss(self, alpha: float, reg: float) -> float:
+        return float(self.loss_async(alpha, reg).item())
+
+
 class _ErrorPoll:
     """Non-blocking look at the persistent sweep's sticky error word: after
     each epoch's launch a copy of the word goes to pinned host memory behind
