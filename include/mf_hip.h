@@ -519,6 +519,26 @@ int mf_als_sweep_probe(const int64_t* entity_ptr, const int32_t* other_ids,
  * and >= 0; reg finite and > 0; counts >= 0 -- else MF_ERR_INVALID, before any
  * device work, with the argument's name in mf_last_error().  n_entities == 0
  * returns MF_OK.
+ *
+ * mf_ials_sweep_cg: the same half-sweep with the per-entity system solved
+ * inexactly by conjugate gradients (Takacs, Pilaszy & Tikk 2011), warm-started
+ * from the entity's current row: arguments as mf_ials_sweep, except that
+ * `features` is read (the start) and written, plus
+ *   cg_steps        number of CG steps per entity, 1..1024
+ * With A and b the matrix and right-hand side above and x the current row:
+ *     res = b - A x;  p = res;  rs = res . res
+ *     repeat cg_steps times:
+ *         if not (rs > 1e-30): stop
+ *         Ap = A p;  a = rs / (p . Ap)
+ *         x += a p;  res -= a Ap;  rs' = res . res
+ *         p = res + (rs' / rs) p;  rs = rs'
+ * A is assembled once per entity (f32-input MFMA, into LDS), so the list rows
+ * are read once whatever cg_steps; a step is O(k^2).  Entities with an empty
+ * list keep their row bit for bit.  An entity whose strengths are all 0 has
+ * b = 0 and gets the CG iterate towards 0 from its current row, NOT exactly
+ * the zero vector (the one visible difference from mf_ials_sweep).  No atomics:
+ * the same input gives the same bits.  Validation as mf_ials_sweep, plus
+ * cg_steps in [1, 1024].
  */
 size_t mf_gramian_workspace_bytes(int64_t n_rows, int32_t n_factors);
 int mf_gramian(const void* features, int64_t n_rows, int32_t n_factors, int32_t dtype,
@@ -527,6 +547,10 @@ int mf_ials_sweep(const int64_t* entity_ptr, const int32_t* other_ids, const voi
                   int32_t n_entities, const void* other_features, const void* gram,
                   void* features, int32_t n_factors, int32_t dtype,
                   double alpha, double reg, void* stream);
+int mf_ials_sweep_cg(const int64_t* entity_ptr, const int32_t* other_ids, const void* strengths,
+                     int32_t n_entities, const void* other_features, const void* gram,
+                     void* features /* read (warm start) and written */, int32_t n_factors,
+                     int32_t dtype, double alpha, double reg, int32_t cg_steps, void* stream);
 
 /* ---------------- multi-GPU replica exchange ----------------------------- */
 

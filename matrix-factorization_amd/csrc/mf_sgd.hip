@@ -303,6 +303,7 @@ extern "C" int mf_warmup(int32_t flags, void* stream) {
     touch_topk(s);
     touch_als(s);
     touch_ials(s);
+    touch_ials_cg(s);
     lt.mark("warmup: other units");
     if (!(flags & MF_FLAG_NO_COOP)) {   // the cooperative launch path (persistent sweeps)
         void* no_args[1] = {nullptr};

@@ -110,6 +110,8 @@ SIGNATURES = {
     "mf_gramian": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P]),
     "mf_ials_sweep": (ctypes.c_int, [
         _P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _F64, _F64, _P]),
+    "mf_ials_sweep_cg": (ctypes.c_int, [
+        _P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _F64, _F64, _I32, _P]),
     "mf_replica_delta": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P]),
     "mf_replica_apply": (ctypes.c_int, [_P, _P, _I64, _I32, _F64, _P]),
     "mf_warmup": (ctypes.c_int, [ctypes.c_int32, _P]),

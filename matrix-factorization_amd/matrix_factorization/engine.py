@@ -1918,8 +1918,8 @@ class FactorALS:
 
 class ImplicitALS(FactorALS):
     """Implicit-feedback ALS (Hu, Koren & Volinsky 2008; mf_gramian +
-    mf_ials_sweep) on FactorALS's CSR lists: the engine's ratings are
-    interaction strengths r >= 0 with confidence 1 + alpha r and preference
+    mf_ials_sweep, or mf_ials_sweep_cg where a sweep is given ``cg_steps``) on
+    FactorALS's CSR lists: the engine's ratings are interaction strengths r >= 0 with confidence 1 + alpha r and preference
     [r > 0]; every other pair counts with confidence 1 and preference 0.  The
     engine must hold float32 linear-kernel parameters, global_mean 0 and zero
     biases (they stay allocated and zero, so predict / topk score x_u . y_i)."""
@@ -1947,27 +1947,35 @@ class ImplicitALS(FactorALS):
             _lib.call("mf_gramian", _tp(F), n, e.k, e.dcode, _tp(self.ws), _tp(out), e.stream)
         return out
 
-    def _isweep(self, csr, n, oq, n_other, q, alpha, reg):
+    def _isweep(self, csr, n, oq, n_other, q, alpha, reg, cg_steps=None):
         e = self.e
         ptr, oth, rr = csr
         self.gramian(oq, n_other, self.gram)
         with torch.cuda.device(e.dev):
-            _lib.call("mf_ials_sweep", _tp(ptr), _tp(oth), _tp(rr), n, _tp(oq), _tp(self.gram),
-                      _tp(q), e.k, e.dcode, float(alpha), float(reg), e.stream)
+            if cg_steps is None:
+                _lib.call("mf_ials_sweep", _tp(ptr), _tp(oth), _tp(rr), n, _tp(oq),
+                          _tp(self.gram), _tp(q), e.k, e.dcode, float(alpha), float(reg),
+                          e.stream)
+            else:
+                _lib.call("mf_ials_sweep_cg", _tp(ptr), _tp(oth), _tp(rr), n, _tp(oq),
+                          _tp(self.gram), _tp(q), e.k, e.dcode, float(alpha), float(reg),
+                          int(cg_steps), e.stream)
 
-    def sweep_users(self, alpha: float, reg: float) -> None:
-        """User rows from the current item side."""
+    def sweep_users(self, alpha: float, reg: float, cg_steps: Optional[int] = None) -> None:
+        """User rows from the current item side.  ``cg_steps`` None: the exact
+        solve (mf_ials_sweep); an integer: that many conjugate-gradient steps
+        per user from its current row (mf_ials_sweep_cg)."""
         e = self.e
-        self._isweep(self.user_csr, e.n_users, e.Q, e.n_items, e.P, alpha, reg)
+        self._isweep(self.user_csr, e.n_users, e.Q, e.n_items, e.P, alpha, reg, cg_steps)
 
-    def sweep_items(self, alpha: float, reg: float) -> None:
-        """Item rows from the current user side."""
+    def sweep_items(self, alpha: float, reg: float, cg_steps: Optional[int] = None) -> None:
+        """Item rows from the current user side (``cg_steps`` as in sweep_users)."""
         e = self.e
-        self._isweep(self.item_csr, e.n_items, e.P, e.n_users, e.Q, alpha, reg)
+        self._isweep(self.item_csr, e.n_items, e.P, e.n_users, e.Q, alpha, reg, cg_steps)
 
-    def epoch(self, alpha: float, reg: float) -> None:
-        self.sweep_users(alpha, reg)
-        self.sweep_items(alpha, reg)
+    def epoch(self, alpha: float, reg: float, cg_steps: Optional[int] = None) -> None:
+        self.sweep_users(alpha, reg, cg_steps)
+        self.sweep_items(alpha, reg, cg_steps)
 
     def loss_async(self, alpha: float, reg: float) -> torch.Tensor:
         """The loss over all n_users x n_items pairs as a device scalar (FP64),

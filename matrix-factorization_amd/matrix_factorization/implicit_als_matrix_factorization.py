@@ -17,7 +17,17 @@ fixed and G = Y^T Y,
 
 and the same for the items with the roles swapped.  A user without
 observations keeps its row; one whose strengths are all 0 gets the zero vector.
-One epoch = users, then items, then the loss.  Everything around fit --
+One epoch = users, then items, then the loss.
+
+``solver="direct"`` (the default) solves each of these k x k systems exactly;
+``solver="cg"`` takes ``cg_steps`` conjugate-gradient steps on it instead,
+started from the entity's current row (Takacs, Pilaszy & Tikk 2011): O(k^2) a
+step against the O(k^3) elimination, and the error a few steps leave is taken
+up by the next epoch's warm start.  The one visible difference besides the
+inexactness: with "cg" an entity whose strengths are all 0 moves towards the
+zero vector by those steps, it is not set to it.
+
+Everything around fit --
 RNG draw order of the initial factors, predict, recommend, recommend_batch,
 pickling -- is KernelMF's (linear kernel, float32 parameters, zero biases, so a
 score is exactly x_u . y_i).
@@ -34,28 +44,48 @@ from .kernel_matrix_factorization import KernelMF
 
 class ImplicitALSMF(KernelMF):
     """Implicit-feedback factor model fitted by ALS on the GPU (mf_gramian +
-    mf_ials_sweep: f32-input MFMA Gramians + LDS elimination per entity).
+    mf_ials_sweep: f32-input MFMA Gramians + LDS elimination per entity, or
+    mf_ials_sweep_cg: the same Gramians + conjugate gradients in LDS).
 
     Arguments: n_factors (1..128), n_epochs, alpha (>= 0: confidence per unit
     of strength), reg (> 0), init_mean, init_sd, min_rating, max_rating,
-    verbose, device.  After fit, ``train_loss`` lists the loss per epoch.
+    verbose, device, solver ("direct" | "cg"), cg_steps (1..1024, used by
+    "cg").  After fit, ``train_loss`` lists the loss per epoch.
     """
+
+    SOLVERS = ("direct", "cg")
+    MAX_CG_STEPS = 1024
 
     def __init__(self, n_factors: int = 100, n_epochs: int = 15, alpha: float = 40.0,
                  reg: float = 1, init_mean: float = 0, init_sd: float = 0.1,
-                 min_rating: int = 0, max_rating: int = 1, verbose: int = 1, device=None):
+                 min_rating: int = 0, max_rating: int = 1, verbose: int = 1, device=None,
+                 solver: str = "direct", cg_steps: int = 3):
         super().__init__(n_factors=n_factors, n_epochs=n_epochs, kernel="linear",
                          reg=reg, init_mean=init_mean, init_sd=init_sd,
                          min_rating=min_rating, max_rating=max_rating, verbose=verbose,
                          dtype="float32", schedule="exact", device=device)
         self.alpha = alpha
+        self.solver = solver
+        self.cg_steps = cg_steps
         self._check_hyper()
+
+    def __setstate__(self, state):
+        # pickles written before the solver choice existed: the exact solve
+        for key, default in (("solver", "direct"), ("cg_steps", 3)):
+            state.setdefault(key, default)
+        super().__setstate__(state)
 
     def _check_hyper(self) -> None:
         if not np.isfinite(self.alpha) or self.alpha < 0:
             raise ValueError(f"alpha must be finite and >= 0, got {self.alpha}")
         if not np.isfinite(self.reg) or self.reg <= 0:
             raise ValueError(f"reg must be finite and > 0, got {self.reg}")
+        if self.solver not in self.SOLVERS:
+            raise ValueError(f"solver must be one of {self.SOLVERS}, got {self.solver!r}")
+        c = self.cg_steps
+        if (isinstance(c, bool) or not isinstance(c, (int, np.integer))
+                or not 1 <= c <= self.MAX_CG_STEPS):
+            raise ValueError(f"cg_steps must be an integer in [1, {self.MAX_CG_STEPS}], got {c!r}")
 
     def _check_strengths(self, y) -> None:
         v = np.asarray(y, dtype=np.float64)
@@ -64,11 +94,12 @@ class ImplicitALSMF(KernelMF):
 
     def _run(self, eng, n_epochs: int, users_only: bool, verbose: int) -> list:
         als = ImplicitALS(eng)
+        cg = int(self.cg_steps) if self.solver == "cg" else None
         pending, loss = [], []
         for epoch in range(n_epochs):
-            als.sweep_users(self.alpha, self.reg)
+            als.sweep_users(self.alpha, self.reg, cg)
             if not users_only:
-                als.sweep_items(self.alpha, self.reg)
+                als.sweep_items(self.alpha, self.reg, cg)
             pending.append(als.loss_async(self.alpha, self.reg))
             if verbose == 1:
                 loss.append(float(pending[-1].item()))
@@ -107,8 +138,10 @@ class ImplicitALSMF(KernelMF):
                      verbose: int = 0):
         """Fold-in with the items frozen: ALSMF.update_users' bookkeeping (known
         users re-initialised, new users appended, same RNG order), then the
-        user half-sweep on the given data -- the exact minimiser, so further
-        epochs repeat it."""
+        user half-sweep on the given data.  With ``solver="direct"`` that is
+        the exact minimiser, so further epochs repeat it; with ``solver="cg"``
+        the re-initialised / new rows are the CG start, and every further
+        epoch takes ``cg_steps`` more steps from the last result."""
         self._check_hyper()
         self._check_strengths(y)
         X, known_users, new_users = self._preprocess_data(X=X, y=y, type="update")

@@ -1,10 +1,12 @@
 #!/usr/bin/env python
-"""Device-event timing of the implicit-ALS kernels (mf_gramian, mf_ials_sweep)
-beside the explicit factor ALS (mf_als_sweep) on the same CSR lists, in one
-process, alternating; the explicit sweep also on its 4-wave kernel
-(MF_ALS_KERNEL=block: k_als_solve, the layout k_ials_solve shares).
+"""Device-event timing of the implicit-ALS kernels (mf_gramian, mf_ials_sweep,
+mf_ials_sweep_cg at --cg-steps steps) beside the explicit factor ALS
+(mf_als_sweep) on the same CSR lists, in one process, alternating; the explicit
+sweep also on its 4-wave kernel (MF_ALS_KERNEL=block: k_als_solve, the layout
+k_ials_solve shares).  The CG rows warm-start from buffers of their own, so the
+other rows see the inputs they saw before those rows existed.
 
-    python tools/bench_ials.py --out profiles/ials/bench_ials.json
+    python tools/bench_ials.py --out profiles/ials/bench_ials_cg.json
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/bench_ials.py --reps 3
 
 Default shape is BASELINE config 5's: 1M users x 100K items, 100M pairs
@@ -45,7 +47,7 @@ def stats(ms):
             "reps": len(a)}
 
 
-def run(k, nu, ni, nnz, reps, warmup, alpha, reg, dev):
+def run(k, nu, ni, nnz, reps, warmup, alpha, reg, dev, cg_steps=3):
     g = torch.Generator(device=dev)
     g.manual_seed(1234 + k)
     u = torch.randint(0, nu, (nnz,), device=dev, generator=g)
@@ -56,6 +58,7 @@ def run(k, nu, ni, nnz, reps, warmup, alpha, reg, dev):
     del u, i, r
     mk = lambda n: (torch.randn((n, k), device=dev, generator=g) * 0.1).contiguous()  # noqa: E731
     P, Q, P2, Q2 = mk(nu), mk(ni), mk(nu), mk(ni)
+    P3, Q3 = mk(nu), mk(ni)                     # the CG rows' warm starts / results
     bu, bi = torch.zeros(nu, device=dev), torch.zeros(ni, device=dev)
     lib = _lib.load()
     ws = torch.empty(max(lib.mf_gramian_workspace_bytes(nu, k), 4) // 4, device=dev)
@@ -76,6 +79,14 @@ def run(k, nu, ni, nnz, reps, warmup, alpha, reg, dev):
         _lib.call("mf_ials_sweep", vp(icsr[0]), vp(icsr[1]), vp(icsr[2]), ni, vp(P), vp(G),
                   vp(Q), k, 0, alpha, reg, st)
 
+    def cg_users():          # same G and fixed side as ials_users, rows in P3
+        _lib.call("mf_ials_sweep_cg", vp(ucsr[0]), vp(ucsr[1]), vp(ucsr[2]), nu, vp(Q), vp(G),
+                  vp(P3), k, 0, alpha, reg, cg_steps, st)
+
+    def cg_items():          # same G and fixed side as ials_items, rows in Q3
+        _lib.call("mf_ials_sweep_cg", vp(icsr[0]), vp(icsr[1]), vp(icsr[2]), ni, vp(P), vp(G),
+                  vp(Q3), k, 0, alpha, reg, cg_steps, st)
+
     def als_users():
         _lib.call("mf_als_sweep", vp(ucsr[0]), vp(ucsr[1]), vp(ucsr[2]), nu, 2.5, vp(bi),
                   vp(Q2), vp(bu), vp(P2), k, 0, reg, st)
@@ -94,7 +105,9 @@ def run(k, nu, ni, nnz, reps, warmup, alpha, reg, dev):
         return go
 
     steps = [("gramian_items", gram_items), ("ials_users", ials_users),
+             ("ials_cg_users", cg_users),
              ("gramian_users", gram_users), ("ials_items", ials_items),
+             ("ials_cg_items", cg_items),
              ("als_users", als_users), ("als_items", als_items),
              ("als_block_users", block(als_users)), ("als_block_items", block(als_items))]
     for _ in range(warmup):
@@ -113,12 +126,12 @@ def run(k, nu, ni, nnz, reps, warmup, alpha, reg, dev):
         torch.cuda.synchronize()
         for name, a, b in evs:
             ms[name].append(a.elapsed_time(b))
-    if not (bool(torch.isfinite(P).all()) and bool(torch.isfinite(Q).all())):
+    if not all(bool(torch.isfinite(t).all()) for t in (P, Q, P3, Q3)):
         raise RuntimeError("non-finite factors after the timed sweeps")
     out = {name: stats(v) for name, v in ms.items()}
     flop = 2.0 * nnz * k * k
-    for name in ("ials_users", "ials_items", "als_users", "als_items", "als_block_users",
-                 "als_block_items"):
+    for name in ("ials_users", "ials_items", "ials_cg_users", "ials_cg_items", "als_users",
+                 "als_items", "als_block_users", "als_block_items"):
         out[name]["tflops"] = flop / (out[name]["median_ms"] * 1e-3) / 1e12
     imp = sum(out[n]["median_ms"] for n in ("gramian_items", "ials_users", "gramian_users",
                                             "ials_items"))
@@ -126,6 +139,12 @@ def run(k, nu, ni, nnz, reps, warmup, alpha, reg, dev):
     out["implicit_epoch_ms"] = imp
     out["explicit_epoch_ms"] = exp
     out["implicit_over_explicit"] = imp / exp
+    cg = sum(out[n]["median_ms"] for n in ("gramian_items", "ials_cg_users", "gramian_users",
+                                           "ials_cg_items"))
+    out["cg_steps"] = cg_steps
+    out["implicit_cg_epoch_ms"] = cg
+    out["implicit_cg_over_explicit"] = cg / exp
+    out["implicit_cg_over_direct"] = cg / imp
     out["explicit_block_epoch_ms"] = (out["als_block_users"]["median_ms"]
                                       + out["als_block_items"]["median_ms"])
     return out
@@ -141,6 +160,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--alpha", type=float, default=40.0)
     ap.add_argument("--reg", type=float, default=0.1)
+    ap.add_argument("--cg-steps", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -150,7 +170,7 @@ def main():
            "alpha": a.alpha, "reg": a.reg, "device": torch.cuda.get_device_name(0), "ranks": {}}
     for k in a.ranks:
         res["ranks"][str(k)] = run(k, a.users, a.items, a.pairs, a.reps, a.warmup, a.alpha,
-                                   a.reg, dev)
+                                   a.reg, dev, a.cg_steps)
         torch.cuda.empty_cache()
     line = json.dumps(res)
     print(line)
