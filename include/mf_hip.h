@@ -397,6 +397,43 @@ int mf_topk_mm(const int32_t* query_users, int32_t n_query, double global_mean,
                int32_t amount, void* workspace, int32_t* out_items,
                void* out_scores, int32_t* overflow, void* stream);
 
+/*
+ * Exact rank of held-out items: for each of n_query users, the 0-based
+ * position of each of its target items among the user's candidate items in
+ * mf_topk's order -- out_rank[t] = number of candidates that come before
+ * target t.  Every top-k metric (precision, recall, NDCG, MAP, MRR at any k)
+ * and AUC is a function of these ranks and of out_candidates, so one pass
+ * serves them all and `amount` has no cap.
+ * Candidates of query q: the items 0..n_items-1 not in q's exclusion list
+ * (same contract as mf_topk: device CSR, both nullable, each list SORTED
+ * ASCENDING, ids outside [0, n_items) ignored; duplicates count once).
+ * out_candidates[q] (device int32, n_query) = their number.
+ * Scores: the unbounded prediction, bit for bit mf_predict(bound_ratings=0)
+ * (a query user of -1: zero row, zero bias).  Order: score descending, then
+ * item id ascending; NaN below every number, all NaNs tie.
+ * Targets: DEVICE CSR target_items[target_ptr[q] .. target_ptr[q+1]) (int32;
+ * any order, repeats allowed, any number per user); out_rank (device int32)
+ * and the workspace are indexed like target_items.  A target outside
+ * [0, n_items), or excluded for its query, gets rank -1.
+ * Counting is integer only (compares, integer adds and atomics), so equal
+ * inputs give equal outputs whatever the launch geometry; nothing of size
+ * n_query * n_items is written.  n_query == 0 returns MF_OK; dtype, kernel
+ * and n_factors (mf_predict's range) are validated before any device work.
+ * workspace: device, >= mf_rank_workspace_bytes(n_query, n_targets, n_items)
+ * with n_targets = target_ptr[n_query].
+ */
+size_t mf_rank_workspace_bytes(int32_t n_query, int64_t n_targets,
+                               int32_t n_items);
+int mf_rank(const int32_t* query_users, int32_t n_query, double global_mean,
+            const void* user_biases, const void* item_biases,
+            const void* user_features, const void* item_features,
+            int32_t n_items, int32_t n_factors, int32_t kernel, int32_t dtype,
+            double gamma, double min_rating, double max_rating,
+            const int64_t* exclude_ptr, const int32_t* exclude_items,
+            const int64_t* target_ptr, const int32_t* target_items,
+            void* workspace, int32_t* out_rank, int32_t* out_candidates,
+            void* stream);
+
 /* ---------------- BaselineModel (bias-only), baseline_model.py ---------- */
 
 /* One bias-SGD epoch over a conflict-free batch schedule: replaces one epoch

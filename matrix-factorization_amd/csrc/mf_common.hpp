@@ -209,5 +209,6 @@ void touch_topk(hipStream_t s);
 void touch_als(hipStream_t s);
 void touch_ials(hipStream_t s);
 void touch_ials_cg(hipStream_t s);
+void touch_rank(hipStream_t s);
 
 }  // namespace mf

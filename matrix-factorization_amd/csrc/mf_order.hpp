@@ -1,0 +1,63 @@
+// mf_order.hpp -- the ranking order shared by top-k (mf_topk.hip) and exact
+// ranking (mf_rank.hip): candidates go by score descending, then by item id
+// ascending, with NaN below every number; and the sorted-list searches both
+// use for the per-query exclusion CSR.
+#pragma once
+
+#include "mf_common.hpp"
+
+namespace mf {
+
+__device__ __forceinline__ uint64_t order_key(double s) {
+    if (s != s) return 1ull;                       // NaN: below every number
+    uint64_t b = (uint64_t)__double_as_longlong(s);
+    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double key_score(uint64_t k) {
+    if (k <= 1ull) return __longlong_as_double(0x7ff8000000000000LL);
+    uint64_t b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
+    return __longlong_as_double((long long)b);
+}
+
+// (key desc, id asc): does (ka, ia) come before (kb, ib)?
+__device__ __forceinline__ bool cand_before(uint64_t ka, int32_t ia, uint64_t kb, int32_t ib) {
+    return ka > kb || (ka == kb && ia < ib);
+}
+
+// is `it` in the sorted id range items[lo, hi)?
+__device__ __forceinline__ bool in_sorted(const int32_t* items, int64_t lo, int64_t hi, int32_t it) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        const int32_t v = items[mid];
+        if (v == it) return true;
+        if (v < it) lo = mid + 1;
+        else hi = mid;
+    }
+    return false;
+}
+// first position in the sorted items[lo, hi) whose id is >= it
+__device__ __forceinline__ int64_t lower_pos(const int32_t* items, int64_t lo, int64_t hi,
+                                             int32_t it) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (items[mid] < it) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ bool excluded(const int64_t* ptr, const int32_t* items, int qy,
+                                         int32_t it) {
+    if (!ptr) return false;
+    int64_t lo = ptr[qy], hi = ptr[qy + 1];          // sorted ascending
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        const int32_t v = items[mid];
+        if (v == it) return true;
+        if (v < it) lo = mid + 1;
+        else hi = mid;
+    }
+    return false;
+}
+
+}  // namespace mf

@@ -304,6 +304,7 @@ extern "C" int mf_warmup(int32_t flags, void* stream) {
     touch_als(s);
     touch_ials(s);
     touch_ials_cg(s);
+    touch_rank(s);
     lt.mark("warmup: other units");
     if (!(flags & MF_FLAG_NO_COOP)) {   // the cooperative launch path (persistent sweeps)
         void* no_args[1] = {nullptr};

@@ -16,23 +16,13 @@
 #include <cstdlib>
 
 #include "mf_common.hpp"
+#include "mf_order.hpp"
 
 namespace mf {
 
 constexpr int kTopkMaxAmount = 2048;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 constexpr int kTopkItemsPerWave = 256;
-
-__device__ __forceinline__ uint64_t order_key(double s) {
-    if (s != s) return 1ull;                       // NaN: below every number
-    uint64_t b = (uint64_t)__double_as_longlong(s);
-    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_score(uint64_t k) {
-    if (k <= 1ull) return __longlong_as_double(0x7ff8000000000000LL);
-    uint64_t b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
 
 template <typename T>
 struct TopkArgs {
@@ -254,11 +244,6 @@ constexpr int kFusedCap = 256;           // list capacity: A2 + 2 chunks <= 256
 
 struct Cand { uint64_t key; int32_t id; };
 
-// (key desc, id asc): does (ka, ia) come before (kb, ib)?
-__device__ __forceinline__ bool cand_before(uint64_t ka, int32_t ia, uint64_t kb, int32_t ib) {
-    return ka > kb || (ka == kb && ia < ib);
-}
-
 // bitonic sort of n (power of two) candidates in LDS by the whole workgroup
 // subset `lanes` (threads t < lanes participate; all threads hit the barriers)
 __device__ __forceinline__ void cand_sort(uint64_t* key, int32_t* id, int n, int t, int lanes) {
@@ -280,42 +265,6 @@ __device__ __forceinline__ void cand_sort(uint64_t* key, int32_t* id, int n, int
             __syncthreads();
         }
     }
-}
-
-// is `it` in the sorted id range items[lo, hi)?
-__device__ __forceinline__ bool in_sorted(const int32_t* items, int64_t lo, int64_t hi, int32_t it) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const int32_t v = items[mid];
-        if (v == it) return true;
-        if (v < it) lo = mid + 1;
-        else hi = mid;
-    }
-    return false;
-}
-// first position in the sorted items[lo, hi) whose id is >= it
-__device__ __forceinline__ int64_t lower_pos(const int32_t* items, int64_t lo, int64_t hi,
-                                             int32_t it) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (items[mid] < it) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ bool excluded(const int64_t* ptr, const int32_t* items, int qy,
-                                         int32_t it) {
-    if (!ptr) return false;
-    int64_t lo = ptr[qy], hi = ptr[qy + 1];          // sorted ascending
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const int32_t v = items[mid];
-        if (v == it) return true;
-        if (v < it) lo = mid + 1;
-        else hi = mid;
-    }
-    return false;
 }
 
 template <typename T>

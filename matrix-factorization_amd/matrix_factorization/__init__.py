@@ -19,7 +19,7 @@ from .baseline_model import BaselineModel
 from .implicit_als_matrix_factorization import ImplicitALSMF
 from .kernel_matrix_factorization import KernelMF
 from .recommender_base import RecommenderBase
-from .utils import train_update_test_split
+from .utils import ranking_metrics_from_ranks, train_update_test_split
 
 __all__ = [
     "ALSMF",
@@ -27,6 +27,7 @@ __all__ = [
     "ImplicitALSMF",
     "KernelMF",
     "RecommenderBase",
+    "ranking_metrics_from_ranks",
     "train_update_test_split",
 ]
 

@@ -1837,6 +1837,76 @@ class SGDEngine:
         self.topk_finish(q)
         return q["items"].cpu().numpy(), q["scores"].cpu().numpy().astype(np.float64)
 
+    # workspace of one rank launch (16 B per target); users whose targets go
+    # beyond this budget take further launches (one user's targets never split)
+    rank_ws_budget = 1 << 30
+
+    def rank(self, users: np.ndarray, tgt_ptr: np.ndarray, tgt_items: np.ndarray,
+             ex_ptr: Optional[np.ndarray] = None,
+             ex_items: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Exact rank of each target item among its user's candidates (mf_rank):
+        (ranks int32[n_targets], n_candidates int32[n_query]).
+
+        ``tgt_ptr`` / ``tgt_items``: CSR targets per internal user id in
+        ``users`` (any order, repeats allowed).  ``ex_ptr`` / ``ex_items``:
+        optional CSR exclusions as for ``topk``.  A target that is out of
+        range or excluded for its user gets rank -1."""
+        if self.bias_only:
+            raise NotImplementedError("ranking is implemented for factor models")
+        users = np.ascontiguousarray(users, np.int32)
+        nq = len(users)
+        tgt_ptr = np.ascontiguousarray(tgt_ptr, np.int64)
+        tgt_items = np.ascontiguousarray(tgt_items, np.int32)
+        if len(tgt_ptr) != nq + 1:
+            raise ValueError("tgt_ptr needs n_query + 1 offsets")
+        tgt_ptr = tgt_ptr - tgt_ptr[0] if nq else tgt_ptr
+        nt = int(tgt_ptr[-1]) if nq else 0
+        if nq and (np.any(np.diff(tgt_ptr) < 0) or nt > len(tgt_items)):
+            raise ValueError("tgt_ptr must be non-decreasing and end within tgt_items")
+        if nq == 0:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32)
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)  # noqa: E731
+        d_users = to(users)
+        d_ex_ptr = d_ex_items = None
+        if ex_ptr is not None:
+            ex_ptr = np.ascontiguousarray(ex_ptr, np.int64)
+            ex_items = np.ascontiguousarray(ex_items, np.int32)
+            if len(ex_ptr) != nq + 1:
+                raise ValueError("ex_ptr needs n_query + 1 offsets")
+            seg = np.repeat(np.arange(nq, dtype=np.int64), np.diff(ex_ptr))
+            ex_items = ex_items[ex_ptr[0]:ex_ptr[-1]]
+            ex_items = ex_items[np.lexsort((ex_items, seg))]
+            d_ex_ptr = to(ex_ptr - ex_ptr[0])
+            d_ex_items = to(ex_items if len(ex_items) else np.zeros(1, np.int32))
+        d_tgt_items = to(tgt_items[:nt] if nt else np.zeros(1, np.int32))
+        ranks = torch.empty(max(nt, 1), dtype=torch.int32, device=self.dev)
+        cands = torch.empty(nq, dtype=torch.int32, device=self.dev)
+        lib = _lib.load()
+        # user chunks: the longest runs whose targets fit the workspace budget
+        cap = max(1, self.rank_ws_budget // max(1, lib.mf_rank_workspace_bytes(1, 1, self.n_items)))
+        bounds = [0]
+        while bounds[-1] < nq:
+            q0 = bounds[-1]
+            q1 = int(np.searchsorted(tgt_ptr, tgt_ptr[q0] + cap, side="right")) - 1
+            bounds.append(min(nq, max(q1, q0 + 1)))
+        with torch.cuda.device(self.dev):
+            for q0, q1 in zip(bounds[:-1], bounds[1:]):
+                b0, b1 = int(tgt_ptr[q0]), int(tgt_ptr[q1])
+                d_ptr = to(tgt_ptr[q0:q1 + 1] - b0)      # chunk-relative offsets
+                ws = torch.empty(max(lib.mf_rank_workspace_bytes(q1 - q0, b1 - b0, self.n_items),
+                                     16), dtype=torch.uint8, device=self.dev)
+                # exclusion offsets stay absolute: the chunk's ptr array starts at row q0
+                dp = None if d_ex_ptr is None else _VOID(d_ex_ptr.data_ptr() + 8 * q0)
+                _lib.call("mf_rank", _VOID(d_users.data_ptr() + 4 * q0), q1 - q0,
+                          self.global_mean, _tp(self.bu), _tp(self.bi), _tp(self.P),
+                          _tp(self.Q), self.n_items, self.k, self.kcode, self.dcode,
+                          self.gamma, self.min_rating, self.max_rating, dp,
+                          None if d_ex_items is None else _tp(d_ex_items), _tp(d_ptr),
+                          _VOID(d_tgt_items.data_ptr() + 4 * b0), _tp(ws),
+                          _VOID(ranks.data_ptr() + 4 * b0),
+                          _VOID(cands.data_ptr() + 4 * q0), self.stream)
+        return ranks[:nt].cpu().numpy(), cands.cpu().numpy()
+
 
 class BiasALS:
     """CSR lists for the bias-model ALS (baseline_model.py:313-348)."""
