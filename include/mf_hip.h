@@ -589,6 +589,89 @@ int mf_ials_sweep_cg(const int64_t* entity_ptr, const int32_t* other_ids, const 
                      void* features /* read (warm start) and written */, int32_t n_factors,
                      int32_t dtype, double alpha, double reg, int32_t cg_steps, void* stream);
 
+/* ---------------- neighbourhood models ----------------------------------- */
+
+/*
+ * ItemItemCF / UserUserCF (collaborative_filtering.py).  One model with the
+ * roles swapped: the ENTITIES are the items (ItemItemCF) or the users
+ * (UserUserCF), the OTHERS are the other side; n = n_others.  With r_ao the
+ * rating of entity a by other o (0 where there is none) and all sums over the
+ * stored entries:
+ *     m_a    = (sum_o r_ao) / n                      (zeros included)
+ *     w_a    = sqrt(max(sum_o r_ao^2 - n m_a^2, 0))
+ *     S[a,b] = (sum_o r_ao r_bo - n m_a m_b) / (w_a w_b),  0 where w_a w_b = 0
+ * Ratings are DEVICE CSR in both orientations: int64 offsets, int32 ids, float
+ * ratings (dtype must be MF_F32).
+ *
+ * mf_cf_stats: replaces the pivot's row / column mean
+ * (collaborative_filtering.py:62-73, :241-252) and the row norms that
+ * sklearn's cosine_similarity takes of the centred matrix (:87-89, :266-268).
+ *   entity_ptr      DEVICE, n_entities + 1 (int64): CSR offsets by entity
+ *   ratings         DEVICE, float, in that CSR's order
+ *   mean, norm      DEVICE, double, n_entities each, written
+ * Each entity's list is summed in list order, in FP64.
+ *
+ * mf_cf_similarity: replaces `_compute_user_similarity` /
+ * `_compute_item_similarity` (collaborative_filtering.py:80-96, :259-274),
+ * where 'cosine' and 'pearson' are the same computation.
+ *   entity_ptr, other_ids, ratings          DEVICE: the entity-major lists
+ *   other_ptr, entity_ids, other_ratings    DEVICE: the other-major lists, every
+ *                   list sorted by entity id ascending
+ *   mean, norm      DEVICE, double: mf_cf_stats' output
+ *   pass_cols       columns of a row held in LDS at once, 0 = automatic
+ *                   (2048), at most 4096; mf_cf_pass_cols() gives the value
+ *                   used (min(that, n_entities)).  A row is done in
+ *                   ceil(n_entities / pass_cols) column ranges, each of which
+ *                   binary-searches the longer other-lists for its range; the
+ *                   result does not depend on pass_cols, bit for bit
+ *   similarity      DEVICE, float, n_entities x n_entities row-major; EVERY
+ *                   element is written (no zeroing by the caller)
+ * One wave owns (entity a, column range): FP64 accumulators in LDS, a's others
+ * applied in a's list order, sum_o deg(o)^2 multiply-adds in all, FP64
+ * epilogue.  No atomics.  With the entity-major lists sorted by other id
+ * ascending, S[a,b] and S[b,a] add the same products in the same order: the
+ * matrix is bitwise symmetric.
+ *
+ * mf_cf_predict: replaces `_predict_rating` and predict's loop
+ * (collaborative_filtering.py:98-190, :276-368).  For pair p with target
+ * entity e = entity_ids[p] and other o = other_ids[p]:
+ *   either id outside its range (-1 = unknown): global_mean;
+ *   candidates: the entities b != e of o's list with r_bo > 0; with more than
+ *     n_neighbors of them the n_neighbors first under (S[e,b] descending,
+ *     b ascending) are kept -- an exact radix select, any list length; the
+ *     keys of lists of up to 1024 entries stay in LDS, longer lists re-read
+ *     S[e,.] on each of the select's passes;
+ *   out[p] = m_e + sum S[e,b] (r_bo - m_b) / sum |S[e,b]| over the kept, in
+ *     FP64 in a fixed order; m_e with no candidate or a zero denominator;
+ *   clipped to [min_rating, max_rating] when bound_ratings.
+ * Differences from the reference: e is never its own neighbour (the
+ * reference's exclusion indexes the compressed list with the uncompressed id),
+ * and ties at the cut go to the lower id (argsort leaves them unspecified).
+ *   other_ptr, list_entity_ids, list_ratings   DEVICE: the other-major lists
+ *   similarity, mean                            DEVICE: as above
+ *   out             DEVICE, double, n_pairs, written
+ * n_pairs is at most 2^25 a call (one workgroup per pair).
+ *
+ * All three: dtype must be MF_F32, counts >= 0, n_neighbors >= 1, pass_cols in
+ * [0, 4096], no NULL for an array that is read or written -- else
+ * MF_ERR_INVALID, before any device work, with the argument's name in
+ * mf_last_error().  n_entities == 0 (n_pairs == 0) returns MF_OK.
+ */
+int mf_cf_stats(const int64_t* entity_ptr, const void* ratings, int32_t n_entities,
+                int32_t n_others, int32_t dtype, double* mean, double* norm, void* stream);
+int32_t mf_cf_pass_cols(int32_t n_entities, int32_t pass_cols);
+int mf_cf_similarity(const int64_t* entity_ptr, const int32_t* other_ids, const void* ratings,
+                     const int64_t* other_ptr, const int32_t* entity_ids,
+                     const void* other_ratings, int32_t n_entities, int32_t n_others,
+                     int32_t dtype, const double* mean, const double* norm, int32_t pass_cols,
+                     void* similarity, void* stream);
+int mf_cf_predict(const int32_t* entity_ids, const int32_t* other_ids, int64_t n_pairs,
+                  const int64_t* other_ptr, const int32_t* list_entity_ids,
+                  const void* list_ratings, const void* similarity, const double* mean,
+                  int32_t n_entities, int32_t n_others, int32_t dtype, int32_t n_neighbors,
+                  double global_mean, double min_rating, double max_rating,
+                  int32_t bound_ratings, double* out, void* stream);
+
 /* ---------------- multi-GPU replica exchange ----------------------------- */
 
 /*

@@ -1,0 +1,402 @@
+// mf_cf.hip -- neighbourhood models (ItemItemCF / UserUserCF): per-entity
+// statistics, the entity x entity similarity from the sparse ratings, and the
+// top-n_neighbors weighted prediction (include/mf_hip.h, "neighbourhood
+// models").
+//
+// One model, roles swapped: the ENTITIES are the items (ItemItemCF) or the
+// users (UserUserCF), the OTHERS are the other side.  Ratings come in both
+// orientations as device CSR (int64 offsets, int32 ids, float ratings).
+//
+// Every kernel here runs ONE WAVE per workgroup (64 threads): a wave's LDS
+// traffic needs no cross-wave hand-off, its barrier is free, and neither
+// kernel has work that four waves could share without atomics.
+//   k_cf_similarity  LDS = 8 B x pass_cols (16 KiB at the automatic 2048
+//                    columns: 10 workgroups = 10 waves per CU by LDS)
+//   k_cf_predict     LDS = 8 KiB of keys + 1 KiB of bins (17 per CU by LDS,
+//                    so the 16-workgroup-per-CU cap is what binds)
+// No floating-point atomics anywhere: equal inputs give equal bits.
+#include <cmath>
+
+#include "mf_common.hpp"
+
+namespace mf {
+namespace cf {
+
+constexpr int kAutoPassCols = 2048;          // 16 KiB of FP64 accumulators
+constexpr int kMaxPassCols = 4096;           // 32 KiB: 5 workgroups per CU still
+constexpr int kSearchMin = 128;              // lists longer than this are range-searched per pass
+constexpr int kKeysLds = 1024;               // longest list whose keys stay in LDS
+constexpr int64_t kMaxGrid = 1 << 25;        // workgroups of one wave: 2^31 threads a launch
+
+// ------------------------------------------------------------- statistics
+// One thread per entity, its list read in list order: sum and sum of squares
+// in FP64 (a float's square is exact in FP64).
+__global__ void __launch_bounds__(kBlock)
+k_cf_stats(const int64_t* __restrict__ ptr, const float* __restrict__ r, int32_t n_entities,
+           double n_others, double* __restrict__ mean, double* __restrict__ norm) {
+    const int64_t a = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (a >= n_entities) return;
+    double s = 0.0, q = 0.0;
+    for (int64_t j = ptr[a], e = ptr[a + 1]; j < e; ++j) {
+        const double v = (double)r[j];
+        s = s + v;
+        q = q + v * v;
+    }
+    const double m = n_others > 0 ? s / n_others : 0.0;
+    const double var = q - n_others * (m * m);
+    mean[a] = m;
+    norm[a] = var > 0.0 ? sqrt(var) : 0.0;
+}
+
+// ------------------------------------------------------------- similarity
+__device__ __forceinline__ int64_t lower_bound(const int32_t* ids, int64_t lo, int64_t hi,
+                                               int32_t key) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (ids[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+struct SimArgs {
+    const int64_t* eptr; const int32_t* eoth; const float* er;   // entity-major
+    const int64_t* optr; const int32_t* oent; const float* orr;  // other-major, ids ascending
+    const double* mean; const double* norm;
+    float* S;
+    int32_t n_entities, n_others, pass_cols;
+};
+
+// Workgroup (a, p): row a of S, columns [p * pass_cols, (p + 1) * pass_cols).
+// acc[b] += r_ao * r_bo for every b of every other o of a, the o's in a's list
+// order with a barrier between them; inside one o the b's are distinct, so no
+// two lanes ever add into one address at a time and the order of the sum is
+// that of a's list.  With a's list ascending in o, S[a,b] and S[b,a] add the
+// same (commuting) products in the same order: S is bitwise symmetric.
+__global__ void __launch_bounds__(kWave)
+k_cf_similarity(const SimArgs A) {
+    extern __shared__ double acc[];
+    const int32_t a = (int32_t)blockIdx.x;
+    const int32_t c0 = (int32_t)blockIdx.y * A.pass_cols;
+    const int32_t nc = min(A.pass_cols, A.n_entities - c0);
+    const bool whole = A.pass_cols >= A.n_entities;
+    const int lane = threadIdx.x;
+    for (int32_t c = lane; c < nc; c += kWave) acc[c] = 0.0;
+    __syncthreads();
+    const double wa = A.norm[a];
+    if (wa > 0.0) {                                   // else the whole row is 0
+        // 64 others of a at a time, one per lane: id, rating, list bounds (and
+        // the range search) are loaded by all lanes at once, so the serial
+        // walk below has one dependent load per other left, and that one --
+        // the first 64 entries of the NEXT other's list -- is issued before
+        // the current other's LDS updates
+        for (int64_t j0 = A.eptr[a], je = A.eptr[a + 1]; j0 < je; j0 += kWave) {
+            double ra_l = 0.0;
+            int64_t lo_l = 0, hi_l = 0;               // lo == hi: nothing to apply
+            if (j0 + lane < je) {
+                const int32_t o = A.eoth[j0 + lane];
+                if ((uint32_t)o < (uint32_t)A.n_others) {
+                    ra_l = (double)A.er[j0 + lane];
+                    lo_l = A.optr[o];
+                    hi_l = A.optr[o + 1];
+                    if (!whole && hi_l - lo_l > kSearchMin) {
+                        lo_l = lower_bound(A.oent, lo_l, hi_l, c0);
+                        hi_l = lower_bound(A.oent, lo_l, hi_l, c0 + nc);
+                    }
+                }
+            }
+            const int cnt = (int)min((int64_t)kWave, je - j0);
+            auto first = [&](int64_t lo, int64_t hi, uint32_t& c, float& r) {
+                const bool in = lo + lane < hi;
+                c = in ? (uint32_t)A.oent[lo + lane] - (uint32_t)c0 : ~0u;
+                r = in ? A.orr[lo + lane] : 0.f;
+            };
+            int64_t lo = __shfl(lo_l, 0, kWave), hi = __shfl(hi_l, 0, kWave);
+            uint32_t c_cur, c_nxt = ~0u;
+            float r_cur, r_nxt = 0.f;
+            first(lo, hi, c_cur, r_cur);
+            for (int s = 0; s < cnt; ++s) {
+                const double ra = __shfl(ra_l, s, kWave);
+                int64_t lo_n = 0, hi_n = 0;
+                if (s + 1 < cnt) {                    // uniform
+                    lo_n = __shfl(lo_l, s + 1, kWave);
+                    hi_n = __shfl(hi_l, s + 1, kWave);
+                    first(lo_n, hi_n, c_nxt, r_nxt);
+                }
+                if (c_cur < (uint32_t)nc) acc[c_cur] = acc[c_cur] + ra * (double)r_cur;
+                for (int64_t t = lo + kWave + lane; t < hi; t += kWave) {
+                    const uint32_t c = (uint32_t)A.oent[t] - (uint32_t)c0;
+                    if (c < (uint32_t)nc) acc[c] = acc[c] + ra * (double)A.orr[t];
+                }
+                __syncthreads();
+                lo = lo_n; hi = hi_n; c_cur = c_nxt; r_cur = r_nxt;
+            }
+        }
+    }
+    const double n = (double)A.n_others, ma = A.mean[a];
+    float* row = A.S + (size_t)a * (size_t)A.n_entities + c0;
+    for (int32_t c = lane; c < nc; c += kWave) {
+        const double wb = A.norm[c0 + c];
+        float s = 0.f;
+        if (wa > 0.0 && wb > 0.0)
+            s = (float)((acc[c] - n * (ma * A.mean[c0 + c])) / (wa * wb));
+        row[c] = s;
+    }
+}
+
+// ------------------------------------------------------------- prediction
+// Total order at the cut: similarity descending, then entity id ascending.
+// key = (monotone image of the float's bits) << 32 | ~id is larger for what
+// comes first, distinct per candidate and never 0 (ids are < 2^31).
+__device__ __forceinline__ uint64_t make_key(float s, int32_t id) {
+    if (s == 0.f) s = 0.f;                            // -0 and +0 tie
+    const uint32_t b = __float_as_uint(s);
+    const uint32_t m = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((uint64_t)m << 32) | (uint32_t)~(uint32_t)id;
+}
+__device__ __forceinline__ float key_sim(uint64_t k) {
+    const uint32_t m = (uint32_t)(k >> 32);
+    return __uint_as_float((m & 0x80000000u) ? (m & 0x7fffffffu) : ~m);
+}
+__device__ __forceinline__ int32_t key_id(uint64_t k) { return (int32_t)~(uint32_t)k; }
+
+struct PredArgs {
+    const int32_t* ent; const int32_t* oth; int64_t n_pairs;
+    const int64_t* optr; const int32_t* oent; const float* orr;
+    const float* S; const double* mean;
+    double* out;
+    int32_t n_entities, n_others, n_neighbors, bound;
+    double global_mean, lo, hi;
+};
+
+// One wave per pair (e, o).  The candidates are o's entries with r > 0 and
+// id != e; their keys stay in LDS for lists of up to kKeysLds entries and are
+// rebuilt from S on every read for longer ones.  With more candidates than
+// n_neighbors the n_neighbors-th largest key is found by an 8-pass radix
+// select (256 integer bins per pass, most significant byte first): exact for
+// any list length, linear in it.
+__global__ void __launch_bounds__(kWave)
+k_cf_predict(const PredArgs A) {
+    __shared__ uint64_t keys[kKeysLds];
+    __shared__ uint32_t bins[256];
+    const int64_t p = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int32_t e = A.ent[p], o = A.oth[p];
+    double pred;
+    if ((uint32_t)e >= (uint32_t)A.n_entities || (uint32_t)o >= (uint32_t)A.n_others) {
+        pred = A.global_mean;                         // unknown id (-1)
+    } else {
+        const int64_t beg = A.optr[o], end = A.optr[o + 1];
+        const int64_t len = end - beg;
+        const bool in_lds = len <= kKeysLds;
+        const float* srow = A.S + (size_t)e * (size_t)A.n_entities;
+        auto build = [&](int64_t t) -> uint64_t {     // 0: not a candidate
+            const int32_t b = A.oent[t];
+            if ((uint32_t)b >= (uint32_t)A.n_entities || b == e || !(A.orr[t] > 0.f)) return 0;
+            return make_key(srow[b], b);
+        };
+        uint32_t cnt = 0;
+        for (int64_t t = beg + lane; t < end; t += kWave) {
+            const uint64_t k = build(t);
+            if (in_lds) keys[t - beg] = k;
+            cnt += k != 0;
+        }
+        cnt = wave_sum(cnt);
+        __syncthreads();
+        auto key_at = [&](int64_t t) -> uint64_t { return in_lds ? keys[t - beg] : build(t); };
+
+        uint64_t cut = 1;                             // keep every candidate (keys are >= 2^31)
+        if (cnt > (uint32_t)A.n_neighbors) {
+            uint64_t prefix = 0;                      // the cut's bytes above the current one
+            uint32_t want = (uint32_t)A.n_neighbors;  // rank of the cut among keys matching prefix
+            for (int sh = 56; sh >= 0; sh -= 8) {
+                for (int c = lane; c < 256; c += kWave) bins[c] = 0;
+                __syncthreads();
+                for (int64_t t = beg + lane; t < end; t += kWave) {
+                    const uint64_t k = key_at(t);
+                    if (k != 0 && (sh == 56 || (k >> (sh + 8)) == prefix))
+                        atomicAdd(&bins[(uint32_t)(k >> sh) & 255u], 1u);
+                }
+                __syncthreads();
+                // lane l owns bins 4l .. 4l+3; suf = count in this lane's bins and above
+                const uint32_t h0 = bins[4 * lane], h1 = bins[4 * lane + 1],
+                               h2 = bins[4 * lane + 2], h3 = bins[4 * lane + 3];
+                const uint32_t own = h0 + h1 + h2 + h3;
+                uint32_t suf = own;
+#pragma unroll
+                for (int d = 1; d < kWave; d <<= 1) {
+                    const uint32_t v = __shfl_down(suf, d, kWave);
+                    if (lane + d < kWave) suf += v;
+                }
+                const unsigned long long has = __ballot(suf >= want);
+                const int src = 63 - __builtin_clzll(has);        // has != 0: cnt > want
+                uint32_t above = suf - own, digit;                // counted above this lane
+                if (above + h3 >= want) digit = 3;
+                else if ((above += h3) + h2 >= want) digit = 2;
+                else if ((above += h2) + h1 >= want) digit = 1;
+                else { above += h1; digit = 0; }
+                digit = (uint32_t)bcast_i32((int)(4 * lane + digit), src);
+                want -= (uint32_t)bcast_i32((int)above, src);
+                prefix = (prefix << 8) | digit;
+                __syncthreads();
+            }
+            cut = prefix;
+        }
+        double num = 0.0, den = 0.0;
+        for (int64_t t = beg + lane; t < end; t += kWave) {
+            const uint64_t k = key_at(t);
+            if (k >= cut) {                           // k == 0 never is
+                const double s = (double)key_sim(k);
+                num = num + s * ((double)A.orr[t] - A.mean[key_id(k)]);
+                den = den + fabs(s);
+            }
+        }
+        num = wave_sum(num);
+        den = wave_sum(den);
+        const double me = A.mean[e];
+        pred = den > 0.0 ? me + num / den : me;
+    }
+    if (A.bound) pred = fmax(A.lo, fmin(A.hi, pred));
+    if (lane == 0) A.out[p] = pred;
+}
+
+inline bool null_arg(const char* fn, const void* const* need, const char* const* names, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!need[i]) {
+            set_error("%s: %s is NULL", fn, names[i]);
+            return true;
+        }
+    return false;
+}
+
+}  // namespace cf
+}  // namespace mf
+
+using namespace mf;
+
+extern "C" int mf_cf_stats(const int64_t* entity_ptr, const void* ratings, int32_t n_entities,
+                           int32_t n_others, int32_t dtype, double* mean, double* norm,
+                           void* stream) {
+    if (dtype != MF_F32) {
+        set_error("mf_cf_stats: dtype=%d (float32 ratings only)", dtype);
+        return MF_ERR_INVALID;
+    }
+    if (n_entities < 0) {
+        set_error("mf_cf_stats: n_entities=%d (must be >= 0)", n_entities);
+        return MF_ERR_INVALID;
+    }
+    if (n_others < 0) {
+        set_error("mf_cf_stats: n_others=%d (must be >= 0)", n_others);
+        return MF_ERR_INVALID;
+    }
+    if (n_entities == 0) return MF_OK;
+    const void* need[] = {entity_ptr, mean, norm};
+    const char* names[] = {"entity_ptr", "mean", "norm"};
+    if (cf::null_arg("mf_cf_stats", need, names, 3)) return MF_ERR_INVALID;
+    hipLaunchKernelGGL(cf::k_cf_stats, dim3((unsigned)((n_entities + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, (hipStream_t)stream, entity_ptr,
+                       static_cast<const float*>(ratings), n_entities, (double)n_others, mean,
+                       norm);
+    MF_HIP_CHECK(hipGetLastError());
+    return MF_OK;
+}
+
+extern "C" int32_t mf_cf_pass_cols(int32_t n_entities, int32_t pass_cols) {
+    if (n_entities <= 0 || pass_cols < 0 || pass_cols > cf::kMaxPassCols) return 0;
+    const int32_t want = pass_cols == 0 ? cf::kAutoPassCols : pass_cols;
+    return want < n_entities ? want : n_entities;
+}
+
+extern "C" int mf_cf_similarity(const int64_t* entity_ptr, const int32_t* other_ids,
+                                const void* ratings, const int64_t* other_ptr,
+                                const int32_t* entity_ids, const void* other_ratings,
+                                int32_t n_entities, int32_t n_others, int32_t dtype,
+                                const double* mean, const double* norm, int32_t pass_cols,
+                                void* similarity, void* stream) {
+    if (dtype != MF_F32) {
+        set_error("mf_cf_similarity: dtype=%d (float32 only)", dtype);
+        return MF_ERR_INVALID;
+    }
+    if (n_entities < 0) {
+        set_error("mf_cf_similarity: n_entities=%d (must be >= 0)", n_entities);
+        return MF_ERR_INVALID;
+    }
+    if (n_others < 0) {
+        set_error("mf_cf_similarity: n_others=%d (must be >= 0)", n_others);
+        return MF_ERR_INVALID;
+    }
+    if (pass_cols < 0 || pass_cols > cf::kMaxPassCols) {
+        set_error("mf_cf_similarity: pass_cols=%d (must be in [0, %d]; 0 = automatic)", pass_cols,
+                  cf::kMaxPassCols);
+        return MF_ERR_INVALID;
+    }
+    if (n_entities == 0) return MF_OK;
+    const void* need[] = {entity_ptr, other_ptr, mean, norm, similarity};
+    const char* names[] = {"entity_ptr", "other_ptr", "mean", "norm", "similarity"};
+    if (cf::null_arg("mf_cf_similarity", need, names, 5)) return MF_ERR_INVALID;
+    cf::SimArgs a;
+    a.eptr = entity_ptr; a.eoth = other_ids; a.er = static_cast<const float*>(ratings);
+    a.optr = other_ptr; a.oent = entity_ids; a.orr = static_cast<const float*>(other_ratings);
+    a.mean = mean; a.norm = norm; a.S = static_cast<float*>(similarity);
+    a.n_entities = n_entities; a.n_others = n_others;
+    a.pass_cols = mf_cf_pass_cols(n_entities, pass_cols);
+    const unsigned n_pass = (unsigned)((n_entities + a.pass_cols - 1) / a.pass_cols);
+    if ((int64_t)n_entities * n_pass > cf::kMaxGrid) {
+        set_error("mf_cf_similarity: n_entities=%d needs %lld workgroups (at most %lld)",
+                  n_entities, (long long)n_entities * n_pass, (long long)cf::kMaxGrid);
+        return MF_ERR_INVALID;
+    }
+    hipLaunchKernelGGL(cf::k_cf_similarity, dim3((unsigned)n_entities, n_pass), dim3(kWave),
+                       (size_t)a.pass_cols * sizeof(double), (hipStream_t)stream, a);
+    MF_HIP_CHECK(hipGetLastError());
+    return MF_OK;
+}
+
+extern "C" int mf_cf_predict(const int32_t* entity_ids, const int32_t* other_ids, int64_t n_pairs,
+                             const int64_t* other_ptr, const int32_t* list_entity_ids,
+                             const void* list_ratings, const void* similarity,
+                             const double* mean, int32_t n_entities, int32_t n_others,
+                             int32_t dtype, int32_t n_neighbors, double global_mean,
+                             double min_rating, double max_rating, int32_t bound_ratings,
+                             double* out, void* stream) {
+    if (dtype != MF_F32) {
+        set_error("mf_cf_predict: dtype=%d (float32 only)", dtype);
+        return MF_ERR_INVALID;
+    }
+    if (n_neighbors < 1) {
+        set_error("mf_cf_predict: n_neighbors=%d (must be >= 1)", n_neighbors);
+        return MF_ERR_INVALID;
+    }
+    if (n_pairs < 0 || n_pairs > cf::kMaxGrid) {
+        set_error("mf_cf_predict: n_pairs=%lld (must be in [0, %lld]: one workgroup per pair)",
+                  (long long)n_pairs, (long long)cf::kMaxGrid);
+        return MF_ERR_INVALID;
+    }
+    if (n_entities < 0) {
+        set_error("mf_cf_predict: n_entities=%d (must be >= 0)", n_entities);
+        return MF_ERR_INVALID;
+    }
+    if (n_others < 0) {
+        set_error("mf_cf_predict: n_others=%d (must be >= 0)", n_others);
+        return MF_ERR_INVALID;
+    }
+    if (n_pairs == 0) return MF_OK;
+    const void* need[] = {entity_ids, other_ids, out};
+    const char* names[] = {"entity_ids", "other_ids", "out"};
+    if (cf::null_arg("mf_cf_predict", need, names, 3)) return MF_ERR_INVALID;
+    if (n_entities > 0 && n_others > 0) {             // else every pair is unknown
+        const void* need2[] = {other_ptr, similarity, mean};
+        const char* names2[] = {"other_ptr", "similarity", "mean"};
+        if (cf::null_arg("mf_cf_predict", need2, names2, 3)) return MF_ERR_INVALID;
+    }
+    cf::PredArgs a;
+    a.ent = entity_ids; a.oth = other_ids; a.n_pairs = n_pairs;
+    a.optr = other_ptr; a.oent = list_entity_ids; a.orr = static_cast<const float*>(list_ratings);
+    a.S = static_cast<const float*>(similarity); a.mean = mean; a.out = out;
+    a.n_entities = n_entities; a.n_others = n_others; a.n_neighbors = n_neighbors;
+    a.bound = bound_ratings ? 1 : 0;
+    a.global_mean = global_mean; a.lo = min_rating; a.hi = max_rating;
+    hipLaunchKernelGGL(cf::k_cf_predict, dim3((unsigned)n_pairs), dim3(kWave), 0,
+                       (hipStream_t)stream, a);
+    MF_HIP_CHECK(hipGetLastError());
+    return MF_OK;
+}

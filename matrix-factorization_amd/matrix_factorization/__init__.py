@@ -9,13 +9,17 @@ train_update_test_split are the host-side surface around them.  ALSMF (no
 reference counterpart: BASELINE config 5) fits the same linear factor model
 by alternating least squares with an MFMA Gramian; ImplicitALSMF (no
 reference counterpart either) fits implicit-feedback strengths by
-confidence-weighted ALS over all user x item pairs.  The
-neighbourhood and content-based models of the reference are outside this
-build's scope.
+confidence-weighted ALS over all user x item pairs.  ItemItemCF and
+UserUserCF are the reference's neighbourhood models
+(collaborative_filtering.py): a float32 similarity matrix built on the GPU
+from the sparse ratings (mf_cf_stats, mf_cf_similarity) and a
+top-n_neighbors weighted prediction (mf_cf_predict).  The content-based model
+of the reference is outside this build's scope.
 """
 
 from .als_matrix_factorization import ALSMF
 from .baseline_model import BaselineModel
+from .collaborative_filtering import ItemItemCF, UserUserCF
 from .implicit_als_matrix_factorization import ImplicitALSMF
 from .kernel_matrix_factorization import KernelMF
 from .recommender_base import RecommenderBase
@@ -25,8 +29,10 @@ __all__ = [
     "ALSMF",
     "BaselineModel",
     "ImplicitALSMF",
+    "ItemItemCF",
     "KernelMF",
     "RecommenderBase",
+    "UserUserCF",
     "ranking_metrics_from_ranks",
     "train_update_test_split",
 ]

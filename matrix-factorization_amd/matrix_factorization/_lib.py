@@ -116,6 +116,13 @@ SIGNATURES = {
         _P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _F64, _F64, _P]),
     "mf_ials_sweep_cg": (ctypes.c_int, [
         _P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _F64, _F64, _I32, _P]),
+    "mf_cf_stats": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "mf_cf_pass_cols": (_I32, [_I32, _I32]),
+    "mf_cf_similarity": (ctypes.c_int, [
+        _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P]),
+    "mf_cf_predict": (ctypes.c_int, [
+        _P, _P, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32,   # ..., n_ent n_oth dtype nn
+        _F64, _F64, _F64, _I32, _P, _P]),                           # mu min max bound out stream
     "mf_replica_delta": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P]),
     "mf_replica_apply": (ctypes.c_int, [_P, _P, _I64, _I32, _F64, _P]),
     "mf_warmup": (ctypes.c_int, [ctypes.c_int32, _P]),
