@@ -331,6 +331,69 @@ int mf_sse_capped(const int32_t* user_ids, const int32_t* item_ids,
                   int32_t max_blocks, double* sse_out, void* stream);
 
 /*
+ * The RMSE pass of epoch e beside the persistent sweep of epoch e + 1
+ * (off unless the engine is asked, MF_SSE_BESIDE=1).
+ *
+ * A handle (mf_beside_create / mf_beside_destroy) owns a flag word in signal
+ * memory and an arrival counter.  mf_sgd_epoch_strata_ticket is
+ * mf_sgd_epoch_strata whose persistent launch carries `ticket` (>= 1, growing
+ * from call to call on one handle): every workgroup counts itself in when it
+ * starts, and the last of the launch's B stores the ticket to the flag --
+ * from then on the whole grid is resident.  Nothing in the sweep waits on
+ * either word; its order and every result bit are those of
+ * mf_sgd_epoch_strata.  Behind whatever the call launched (persistent, one
+ * launch per stratum, nothing after an error) it enqueues a
+ * hipStreamWriteValue32 of the same ticket on `stream`: the backstop.
+ * `beside` NULL: plain mf_sgd_epoch_strata.  kernel_attrs (nullable, int32[3],
+ * with MF_FLAG_PREPARE): the persistent kernel the plan runs as {registers per
+ * thread, waves per workgroup, LDS bytes}, zeros if it runs per stratum.
+ *
+ * mf_sse_beside, called after that launch, makes `stream` (a side stream)
+ * wait until the flag is >= ticket (hipStreamWaitValue32) and then runs
+ * mf_sse_capped there with one workgroup per compute unit.  The wait can only
+ * be for something already enqueued; at worst the pass starts when the sweep
+ * ends.  kernel_attrs non-NULL: no wait and no launch, the pass kernel's
+ * attributes as above (`beside` may be NULL).
+ *
+ * mf_beside_fit (host arithmetic only): 1 if exactly one workgroup of the
+ * pass fits on a compute unit beside one resident sweep workgroup and a second
+ * does not -- registers per SIMD (allocated per wave in granules of 8, a
+ * workgroup's waves dealt evenly over cu_simds SIMDs of simd_regs registers)
+ * and LDS (cu_lds bytes); else 0.  mf_beside_supported: 1 if the current
+ * device can hipStreamWaitValue32.
+ */
+int mf_beside_supported(void);
+int mf_beside_create(void** handle);
+void mf_beside_destroy(void* handle);
+int mf_beside_fit(int32_t sweep_regs, int32_t sweep_waves, int32_t sweep_lds,
+                  int32_t pass_regs, int32_t pass_waves, int32_t pass_lds,
+                  int32_t simd_regs, int32_t cu_simds, int32_t cu_lds);
+int mf_sgd_epoch_strata_ticket(
+    const int32_t* user_ids, const int32_t* item_ids, const void* ratings, int64_t n_positions,
+    int32_t n_blocks, const int32_t* user_bounds, const int32_t* item_bounds,
+    const int64_t* block_steps, int32_t n_slots, int32_t max_block_items,
+    int32_t max_block_users, const int32_t* strata_seq, int32_t n_seq, uint32_t seed,
+    double global_mean, void* user_biases, void* item_biases, void* user_features,
+    void* item_features, int32_t n_users, int32_t n_items, int32_t n_factors, int32_t kernel,
+    int32_t dtype, double gamma, double lr, double reg, double min_rating, double max_rating,
+    int32_t update_user_params, int32_t update_item_params, int32_t flags, void* workspace,
+    size_t workspace_bytes, void* beside, int32_t ticket, int32_t* kernel_attrs, void* stream,
+    double* kernel_ms);
+int mf_sse_beside(void* beside, int32_t ticket, const int32_t* user_ids,
+                  const int32_t* item_ids, const void* ratings, int64_t n_ratings,
+                  double global_mean, const void* user_biases, const void* item_biases,
+                  const void* user_features, const void* item_features, int32_t n_users,
+                  int32_t n_items, int32_t n_factors, int32_t kernel, int32_t dtype,
+                  double gamma, double min_rating, double max_rating,
+                  const int64_t* slice_offsets, int32_t n_slices, void* workspace,
+                  double* sse_out, void* stream, int32_t* kernel_attrs);
+/* Up to MF_PERMUTE_MAX_JOBS device arrays copied in one launch (the parameter
+ * snapshot of the overlapped RMSE pass): n_bytes[j] a multiple of 4, arrays
+ * 16-byte aligned; dst / src / n_bytes are HOST arrays of n_jobs. */
+int mf_copy_arrays(int32_t n_jobs, void* const* dst, const void* const* src,
+                   const int64_t* n_bytes, void* stream);
+
+/*
  * Predictions for (user, item) pairs -- replaces `_predict`
  * (kernel_matrix_factorization.py:448-541).  An id of -1 is unknown: zero
  * bias and an all-zero factor vector (:487-499).  Clipped to

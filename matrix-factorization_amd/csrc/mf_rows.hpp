@@ -1162,6 +1162,9 @@ struct SseParams {
     int32_t k; int32_t kernel; double gamma, lo, hi;
     double* partials; double* sse_out; hipStream_t stream; SliceTab S;
     int32_t max_blocks;      // > 0: at most this many workgroups (mf_sse_capped)
+    // nullable: no launch -- receives the pass kernel as {registers per
+    // thread, waves per workgroup, LDS bytes} (hipFuncGetAttributes)
+    int32_t* attrs_out = nullptr;
 };
 
 template <typename T>
@@ -1345,6 +1348,14 @@ struct SseRun {
                           : k_sse_phased<T, W, GS, V, KERN, 16, false>;
         }
         if (var == 0 && !u24) var = 7;                    // its own occupancy entry
+        if (p.attrs_out) {
+            hipFuncAttributes fa;
+            MF_HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kfn)));
+            p.attrs_out[0] = fa.numRegs;
+            p.attrs_out[1] = kBlock / kWave;
+            p.attrs_out[2] = (int32_t)fa.sharedSizeBytes;
+            return MF_OK;
+        }
         static int resident_tab[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // per instantiation and variant
         int& resident = resident_tab[var];
         if (resident == 0) {

@@ -8,6 +8,7 @@
 // follow a fixed DPP order instead of BLAS ddot's.
 #include <atomic>
 #include <algorithm>
+#include <new>
 #include <type_traits>
 #include <vector>
 
@@ -263,6 +264,14 @@ bool strata_inject_fail() {
         if (g_strata_inject.compare_exchange_weak(v, v - 1)) return true;
     return false;
 }
+
+// State of one engine's "RMSE pass beside the next sweep" (mf_beside_create):
+// the flag word a side stream waits on, in signal memory, and the arrival
+// counter of the persistent launches that carry a ticket.
+struct Beside {
+    int32_t* flag;
+    int32_t* arrive;
+};
 }  // namespace mf
 
 extern "C" int mf_strata_set_probe(int64_t* probe) {
@@ -366,7 +375,10 @@ static int strata_epoch(const int32_t* user_ids, const int32_t* item_ids,
                                    double min_rating, double max_rating,
                                    int32_t update_user_params, int32_t update_item_params,
                                    int32_t flags, void* workspace, size_t workspace_bytes,
-                                   void* stream, double* kernel_ms, void* dq, void* dbi) {
+                                   void* stream, double* kernel_ms, void* dq, void* dbi,
+                                   const mf::Beside* beside = nullptr, int32_t ticket = 0,
+                                   int32_t* attrs_out = nullptr) {
+    if (attrs_out) attrs_out[0] = attrs_out[1] = attrs_out[2] = 0;
     if (n_positions < 0 || n_blocks < 0 || n_seq < 0 || n_users < 0 || n_items < 0 ||
         max_block_items < 0 || max_block_users < 0 || n_slots < 1) {
         set_error("negative size");
@@ -407,6 +419,10 @@ static int strata_epoch(const int32_t* user_ids, const int32_t* item_ids,
                    min_rating, max_rating, update_user_params ? 1 : 0,
                    update_item_params ? 1 : 0, flags, workspace, workspace_bytes, n_users,
                    (hipStream_t)stream, kernel_ms, n_items, dq, dbi, n_positions};
+    if (beside) {
+        P.tk_arrive = beside->arrive; P.tk_flag = beside->flag; P.tk_val = ticket;
+    }
+    P.attrs_out = attrs_out;
     if (dtype == MF_F32) return strata_launch_f32(P);
     if (dtype == MF_F64) return strata_launch_f64(P);
     set_error("unknown dtype code %d", dtype);
@@ -465,15 +481,16 @@ extern "C" size_t mf_sse_workspace_bytes(int64_t n_ratings) {
     return sizeof(double) * (size_t)kSseMaxBlocks;
 }
 
-extern "C" int mf_sse_capped(const int32_t* user_ids, const int32_t* item_ids,
-                             const void* ratings, int64_t n_ratings,
-                             double global_mean, const void* user_biases,
-                             const void* item_biases, const void* user_features,
-                             const void* item_features, int32_t n_users, int32_t n_items,
-                             int32_t n_factors, int32_t kernel, int32_t dtype, double gamma,
-                             double min_rating, double max_rating,
-                             const int64_t* slice_offsets, int32_t n_slices, void* workspace,
-                             int32_t max_blocks, double* sse_out, void* stream) {
+// mf_sse_capped; attrs_out (nullable): no launch, the pass kernel's attributes
+static int sse_capped(const int32_t* user_ids, const int32_t* item_ids, const void* ratings,
+                      int64_t n_ratings, double global_mean, const void* user_biases,
+                      const void* item_biases, const void* user_features,
+                      const void* item_features, int32_t n_users, int32_t n_items,
+                      int32_t n_factors, int32_t kernel, int32_t dtype, double gamma,
+                      double min_rating, double max_rating, const int64_t* slice_offsets,
+                      int32_t n_slices, void* workspace, int32_t max_blocks, double* sse_out,
+                      void* stream, int32_t* attrs_out) {
+    if (attrs_out) attrs_out[0] = attrs_out[1] = attrs_out[2] = 0;
     if (n_ratings < 0 || !sse_out || !workspace || n_users < 0 || n_items < 0 ||
         (slice_offsets && (n_slices < 1 || n_slices > kMaxSlices))) {
         set_error("mf_sse: bad arguments (n_slices must be in [1, %d])", kMaxSlices);
@@ -493,7 +510,8 @@ extern "C" int mf_sse_capped(const int32_t* user_ids, const int32_t* item_ids,
         S.n = 1; S.off[0] = 0; S.off[1] = n_ratings;
     }
     if (n_ratings == 0) {
-        MF_HIP_CHECK(hipMemsetAsync(sse_out, 0, sizeof(double), (hipStream_t)stream));
+        if (!attrs_out)
+            MF_HIP_CHECK(hipMemsetAsync(sse_out, 0, sizeof(double), (hipStream_t)stream));
         return MF_OK;
     }
     if (max_blocks < 0) {
@@ -504,10 +522,227 @@ extern "C" int mf_sse_capped(const int32_t* user_ids, const int32_t* item_ids,
                 item_biases, user_features, item_features, n_users, n_items, n_factors,
                 kernel, gamma, min_rating, max_rating, (double*)workspace, sse_out,
                 (hipStream_t)stream, S, max_blocks};
+    P.attrs_out = attrs_out;
     if (dtype == MF_F32) return sse_launch_f32(P);
     if (dtype == MF_F64) return sse_launch_f64(P);
     set_error("unknown dtype code %d", dtype);
     return MF_ERR_INVALID;
+}
+
+extern "C" int mf_sse_capped(const int32_t* user_ids, const int32_t* item_ids,
+                             const void* ratings, int64_t n_ratings,
+                             double global_mean, const void* user_biases,
+                             const void* item_biases, const void* user_features,
+                             const void* item_features, int32_t n_users, int32_t n_items,
+                             int32_t n_factors, int32_t kernel, int32_t dtype, double gamma,
+                             double min_rating, double max_rating,
+                             const int64_t* slice_offsets, int32_t n_slices, void* workspace,
+                             int32_t max_blocks, double* sse_out, void* stream) {
+    return sse_capped(user_ids, item_ids, ratings, n_ratings, global_mean, user_biases,
+                      item_biases, user_features, item_features, n_users, n_items, n_factors,
+                      kernel, dtype, gamma, min_rating, max_rating, slice_offsets, n_slices,
+                      workspace, max_blocks, sse_out, stream, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// The RMSE pass beside the next epoch's persistent sweep.
+extern "C" int mf_beside_supported(void) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&v, hipDeviceAttributeCanUseStreamWaitValue, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return v ? 1 : 0;
+}
+
+extern "C" int mf_beside_create(void** handle) {
+    if (!handle) {
+        set_error("mf_beside_create: NULL handle");
+        return MF_ERR_INVALID;
+    }
+    *handle = nullptr;
+    Beside* b = new (std::nothrow) Beside{nullptr, nullptr};
+    if (!b) {
+        set_error("mf_beside_create: out of host memory");
+        return MF_ERR_NOMEM;
+    }
+    // (signal memory: one 8-byte word; the flag is its low 32 bits)
+    hipError_t e = hipExtMallocWithFlags(reinterpret_cast<void**>(&b->flag), 8,
+                                         hipMallocSignalMemory);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b->arrive), sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(b->flag, 0, 8);
+    if (e == hipSuccess) e = hipMemset(b->arrive, 0, sizeof(int32_t));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        if (b->flag) (void)hipFree(b->flag);
+        if (b->arrive) (void)hipFree(b->arrive);
+        delete b;
+        (void)hipGetLastError();
+        return hip_fail(e, "mf_beside_create");
+    }
+    *handle = b;
+    return MF_OK;
+}
+
+extern "C" void mf_beside_destroy(void* handle) {
+    Beside* b = static_cast<Beside*>(handle);
+    if (!b) return;
+    (void)hipFree(b->flag);
+    (void)hipFree(b->arrive);
+    delete b;
+}
+
+extern "C" int mf_beside_fit(int32_t sweep_regs, int32_t sweep_waves, int32_t sweep_lds,
+                             int32_t pass_regs, int32_t pass_waves, int32_t pass_lds,
+                             int32_t simd_regs, int32_t cu_simds, int32_t cu_lds) {
+    if (sweep_regs < 1 || sweep_waves < 1 || pass_regs < 1 || pass_waves < 1 || sweep_lds < 0 ||
+        pass_lds < 0 || simd_regs < 1 || cu_simds < 1 || cu_lds < 1)
+        return 0;
+    // registers are allocated per wave in granules of 8; a workgroup's waves
+    // are dealt evenly over the CU's SIMDs
+    auto per_simd = [&](int32_t regs, int32_t waves) {
+        return (int64_t)((regs + 7) / 8 * 8) * ((waves + cu_simds - 1) / cu_simds);
+    };
+    const int64_t sw = per_simd(sweep_regs, sweep_waves), ps = per_simd(pass_regs, pass_waves);
+    const bool one = sw + ps <= simd_regs && (int64_t)sweep_lds + pass_lds <= cu_lds;
+    const bool two = sw + 2 * ps <= simd_regs && (int64_t)sweep_lds + 2 * (int64_t)pass_lds <= cu_lds;
+    return one && !two ? 1 : 0;
+}
+
+extern "C" int mf_sgd_epoch_strata_ticket(
+    const int32_t* user_ids, const int32_t* item_ids, const void* ratings, int64_t n_positions,
+    int32_t n_blocks, const int32_t* user_bounds, const int32_t* item_bounds,
+    const int64_t* block_steps, int32_t n_slots, int32_t max_block_items,
+    int32_t max_block_users, const int32_t* strata_seq, int32_t n_seq, uint32_t seed,
+    double global_mean, void* user_biases, void* item_biases, void* user_features,
+    void* item_features, int32_t n_users, int32_t n_items, int32_t n_factors, int32_t kernel,
+    int32_t dtype, double gamma, double lr, double reg, double min_rating, double max_rating,
+    int32_t update_user_params, int32_t update_item_params, int32_t flags, void* workspace,
+    size_t workspace_bytes, void* beside, int32_t ticket, int32_t* kernel_attrs, void* stream,
+    double* kernel_ms) {
+    const Beside* b = static_cast<const Beside*>(beside);
+    if (b && ticket < 1) {
+        set_error("mf_sgd_epoch_strata_ticket: ticket < 1");
+        return MF_ERR_INVALID;
+    }
+    int rc = strata_epoch(user_ids, item_ids, ratings, n_positions, n_blocks, user_bounds,
+                          item_bounds, block_steps, n_slots, max_block_items, max_block_users,
+                          strata_seq, n_seq, seed, global_mean, user_biases, item_biases,
+                          user_features, item_features, n_users, n_items, n_factors, kernel,
+                          dtype, gamma, lr, reg, min_rating, max_rating, update_user_params,
+                          update_item_params, flags, workspace, workspace_bytes, stream,
+                          kernel_ms, nullptr, nullptr, b, ticket, kernel_attrs);
+    // the backstop: whatever strata_epoch did -- a persistent launch, one
+    // launch per stratum, a refused cooperative launch, an error return --
+    // the same ticket is written behind it on the launch stream, so a side
+    // stream waiting for it (mf_sse_beside) is released at the latest when
+    // the sweep has ended
+    if (b && !(flags & MF_FLAG_PREPARE)) {
+        const hipError_t e = hipStreamWriteValue32((hipStream_t)stream, b->flag,
+                                                   (uint32_t)ticket, 0);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (rc == MF_OK) rc = hip_fail(e, "hipStreamWriteValue32 (ticket backstop)");
+        }
+    }
+    return rc;
+}
+
+extern "C" int mf_sse_beside(void* beside, int32_t ticket, const int32_t* user_ids,
+                             const int32_t* item_ids, const void* ratings, int64_t n_ratings,
+                             double global_mean, const void* user_biases,
+                             const void* item_biases, const void* user_features,
+                             const void* item_features, int32_t n_users, int32_t n_items,
+                             int32_t n_factors, int32_t kernel, int32_t dtype, double gamma,
+                             double min_rating, double max_rating,
+                             const int64_t* slice_offsets, int32_t n_slices, void* workspace,
+                             double* sse_out, void* stream, int32_t* kernel_attrs) {
+    int dev = 0, cus = 0;
+    MF_HIP_CHECK(hipGetDevice(&dev));
+    MF_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (cus < 1) {
+        set_error("mf_sse_beside: no compute units reported");
+        return MF_ERR_HIP;
+    }
+    if (!kernel_attrs) {
+        const Beside* b = static_cast<const Beside*>(beside);
+        if (!b || ticket < 1) {
+            set_error("mf_sse_beside: NULL handle or ticket < 1");
+            return MF_ERR_INVALID;
+        }
+        MF_HIP_CHECK(hipStreamWaitValue32((hipStream_t)stream, b->flag, (uint32_t)ticket,
+                                          hipStreamWaitValueGte, 0xFFFFFFFFu));
+    }
+    return sse_capped(user_ids, item_ids, ratings, n_ratings, global_mean, user_biases,
+                      item_biases, user_features, item_features, n_users, n_items, n_factors,
+                      kernel, dtype, gamma, min_rating, max_rating, slice_offsets, n_slices,
+                      workspace, cus, sse_out, stream, kernel_attrs);
+}
+
+namespace mf {
+struct CopyJobs {
+    const char* src[MF_PERMUTE_MAX_JOBS];
+    char* dst[MF_PERMUTE_MAX_JOBS];
+    int64_t end16[MF_PERMUTE_MAX_JOBS];   // running total of whole 16-B chunks
+    int64_t bytes[MF_PERMUTE_MAX_JOBS];
+    int32_t n;
+};
+
+// Up to 4 arrays copied in one launch (the parameter snapshot): the 16-B
+// chunks of all jobs form one index space; the < 16 B tails go word by word.
+__global__ __launch_bounds__(kBlock) void k_copy_jobs(CopyJobs J) {
+    const int64_t total = J.end16[J.n - 1];
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total;
+         t += (int64_t)gridDim.x * kBlock) {
+        int j = 0;
+        while (t >= J.end16[j]) ++j;                     // (j < n: t < total)
+        const int64_t c = t - (j ? J.end16[j - 1] : 0);
+        reinterpret_cast<uint4*>(J.dst[j])[c] = reinterpret_cast<const uint4*>(J.src[j])[c];
+    }
+    if (blockIdx.x == 0) {
+        for (int j = 0; j < J.n; ++j) {
+            const int64_t done = (J.bytes[j] / 16) * 16;
+            const int64_t o = done + 4 * (int64_t)threadIdx.x;
+            if (o < J.bytes[j])
+                *reinterpret_cast<uint32_t*>(J.dst[j] + o) =
+                    *reinterpret_cast<const uint32_t*>(J.src[j] + o);
+        }
+    }
+}
+}  // namespace mf
+
+extern "C" int mf_copy_arrays(int32_t n_jobs, void* const* dst, const void* const* src,
+                              const int64_t* n_bytes, void* stream) {
+    if (n_jobs < 0 || n_jobs > MF_PERMUTE_MAX_JOBS || (n_jobs > 0 && (!dst || !src || !n_bytes))) {
+        set_error("mf_copy_arrays: bad arguments");
+        return MF_ERR_INVALID;
+    }
+    CopyJobs J{};
+    int64_t run = 0;
+    for (int32_t j = 0; j < n_jobs; ++j) {
+        if (n_bytes[j] < 0 || n_bytes[j] % 4 != 0 ||
+            (n_bytes[j] > 0 && (!dst[j] || !src[j] ||
+                                (reinterpret_cast<uintptr_t>(dst[j]) |
+                                 reinterpret_cast<uintptr_t>(src[j])) % 16 != 0))) {
+            set_error("mf_copy_arrays: job %d invalid (sizes in multiples of 4 bytes, 16-byte "
+                      "aligned arrays)", j);
+            return MF_ERR_INVALID;
+        }
+        if (n_bytes[j] == 0) continue;
+        J.src[J.n] = static_cast<const char*>(src[j]);
+        J.dst[J.n] = static_cast<char*>(dst[j]);
+        J.bytes[J.n] = n_bytes[j];
+        run += n_bytes[j] / 16;
+        J.end16[J.n] = run;
+        ++J.n;
+    }
+    if (J.n == 0) return MF_OK;
+    const int64_t need = (run / 4 + kBlock - 1) / kBlock;            // ~four chunks per thread
+    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, 8192));
+    hipLaunchKernelGGL(k_copy_jobs, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, J);
+    MF_HIP_CHECK(hipGetLastError());
+    return MF_OK;
 }
 
 extern "C" int mf_sse(const int32_t* user_ids, const int32_t* item_ids,

@@ -88,7 +88,28 @@ struct StrataArgs {
     int32_t* xtab;           // nullable: MF_FLAG_L2_HANDOFF -- per workgroup ((base+1) << 4) | XCC id
     int32_t early;           // persistent, C > 1: poll the next position's user range during
                              // the current block (0: MF_FLAG_NO_EARLY_POLL)
+    // resident ticket (nullable; persistent kernels, mf_sgd_epoch_strata_ticket):
+    // every workgroup counts itself in at its start, and the last of the
+    // launch's B stores `tk_val` to `tk_flag` -- from then on the whole grid
+    // is resident.  Nothing in the sweep waits on either word.
+    int32_t* tk_arrive;      // arrival counter, grows by B per launch (no memset)
+    int32_t* tk_flag;        // the flag word a side stream waits on (mf_sse_beside)
+    int32_t tk_val;
 };
+
+// The resident ticket of a persistent launch (StrataArgs::tk_*): called once
+// by thread 0 of every workgroup.  The flag carries no data, only "all B
+// workgroups of this launch have started".
+template <typename T>
+__device__ __forceinline__ void strata_ticket_arrive(const StrataArgs<T>& A) {
+    if (!A.tk_flag) return;
+    const unsigned old = (unsigned)__hip_atomic_fetch_add(A.tk_arrive, 1, __ATOMIC_RELAXED,
+                                                          __HIP_MEMORY_SCOPE_AGENT);
+    // (a count that ever wrapped would only leave the flag to the launcher's
+    // backstop write behind the launch)
+    if ((old + 1u) % (unsigned)A.B == 0u)
+        __hip_atomic_store(A.tk_flag, A.tk_val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // first step of block `blk` in this epoch (mirrored by engine.strata_mix)
 __host__ __device__ inline uint32_t strata_mix(uint32_t seed, uint32_t blk) {
@@ -616,6 +637,7 @@ __global__ __launch_bounds__(NW * kWave) void k_sgd_strata_epoch(StrataArgs<T> A
     const int ilo = A.ibnd[w], nqi = A.ibnd[w + 1] - ilo;
     if (threadIdx.x == 0) {               // this workgroup's count at the end of the last launch
         s_base = __hip_atomic_load(done + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        strata_ticket_arrive(A);
         if (A.xtab) {                     // publish (launch tag, XCC id); tag != 0,
             unsigned v;                   // so a zeroed entry never looks published
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
@@ -959,8 +981,10 @@ __global__ __launch_bounds__(NW * kWave) void k_sgd_strata_stream(StrataArgs<T> 
     auto now = []() __attribute__((always_inline)) {
         return (uint32_t)__builtin_amdgcn_s_memrealtime();
     };
-    if (threadIdx.x == 0)
+    if (threadIdx.x == 0) {
         s_base = __hip_atomic_load(done + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        strata_ticket_arrive(A);
+    }
     const Hyper<T> h = hyper_regs(A.h);
     strata_stage_slab<T, W, KERN, TH>(A, ilo, nqi, Qs, Bis);
     for (int p = threadIdx.x; p < n_seq; p += TH) {
@@ -1355,6 +1379,12 @@ struct StrataParams {
     hipStream_t stream; double* kernel_ms;
     int64_t n_items; void* dq; void* dbi;    // delta-out (nullable)
     int64_t n_positions;                     // entries of each triple array
+    // resident ticket of the persistent launch (nullable; StrataArgs::tk_*)
+    int32_t* tk_arrive = nullptr; int32_t* tk_flag = nullptr; int32_t tk_val = 0;
+    // nullable, with MF_FLAG_PREPARE: receives the persistent kernel this plan
+    // would run as {registers per thread, waves per workgroup, LDS bytes}
+    // (hipFuncGetAttributes), or {0, 0, 0} when it would run per stratum
+    int32_t* attrs_out = nullptr;
 };
 
 // workspace of the persistent kernel (int32): done[B] (position counters,
@@ -1499,6 +1529,8 @@ struct StrataRun {
         a.probe = strata_probe_ptr();
         a.xtab = nullptr;
         a.early = (p.flags & MF_FLAG_NO_EARLY_POLL) ? 0 : 1;
+        a.tk_arrive = p.tk_arrive; a.tk_flag = p.tk_flag; a.tk_val = p.tk_val;
+        if (p.attrs_out) p.attrs_out[0] = p.attrs_out[1] = p.attrs_out[2] = 0;
         hipEvent_t ev[2] = {nullptr, nullptr};
         if (p.kernel_ms && !(p.flags & MF_FLAG_PREPARE)) {
             MF_HIP_CHECK(hipEventCreate(&ev[0]));
@@ -1549,6 +1581,14 @@ struct StrataRun {
                 persistent = strata_coresident(reinterpret_cast<const void*>(efn), p.B, lds, TH);
             }
             lt0.mark("strata_coresident");
+            if (p.attrs_out && persistent) {
+                hipFuncAttributes fa;
+                MF_HIP_CHECK(hipFuncGetAttributes(
+                    &fa, sfn ? sfn : reinterpret_cast<const void*>(efn)));
+                p.attrs_out[0] = fa.numRegs;
+                p.attrs_out[1] = NW;
+                p.attrs_out[2] = (int32_t)(sfn ? slds : lds) + (int32_t)fa.sharedSizeBytes;
+            }
             if (p.flags & MF_FLAG_PREPARE) return MF_OK;       // attributes / occupancy only
             if (persistent) {
                 const LaunchTrace lt1;

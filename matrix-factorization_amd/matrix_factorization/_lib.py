@@ -80,6 +80,20 @@ SIGNATURES = {
     "mf_sse_capped": (ctypes.c_int, [
         _P, _P, _P, _I64, _F64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F64,
         _F64, _F64, _P, _I32, _P, _I32, _P, _P]),
+    "mf_beside_supported": (ctypes.c_int, []),
+    "mf_beside_create": (ctypes.c_int, [_P]),
+    "mf_beside_destroy": (None, [_P]),
+    "mf_beside_fit": (ctypes.c_int, [_I32] * 9),
+    "mf_sgd_epoch_strata_ticket": (ctypes.c_int, [
+        _P, _P, _P, _I64, _I32, _P, _P, _P, _I32, _I32, _I32, _P, _I32, ctypes.c_uint32,
+        _F64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F64, _F64, _F64, _F64, _F64,
+        _I32, _I32, _I32, _P, ctypes.c_size_t,
+        _P, _I32, _P, _P, _PD]),                      # beside, ticket, attrs, stream, ms
+    "mf_sse_beside": (ctypes.c_int, [
+        _P, _I32,                                     # beside, ticket
+        _P, _P, _P, _I64, _F64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F64,
+        _F64, _F64, _P, _I32, _P, _P, _P, _P]),       # ..., ws, out, stream, attrs
+    "mf_copy_arrays": (ctypes.c_int, [_I32, _P, _P, _P, _P]),
     "mf_predict": (ctypes.c_int, [
         _P, _P, _I64, _F64, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64,
         _F64, _I32, _P, _P]),

@@ -692,6 +692,8 @@ class SGDEngine:
         self.sse_buf = torch.zeros(16, dtype=torch.float64, device=self.dev)
         self.P = self.Q = self.bu = self.bi = None
         self._ov = None              # sse_overlap state (side stream, snapshot)
+        self._bs = None              # beside-mode state (_beside_state); False = not eligible
+        self.beside_info = None      # the kernels' attributes the fit check was asked with
 
     # ---------------------------------------------------------- plumbing
     @property
@@ -1284,7 +1286,7 @@ class SGDEngine:
 
     def epoch_strata(self, seq: Optional[np.ndarray], seed: int, lr: float, reg: float,
                      update_user: bool = True, update_item: bool = True, timing=False,
-                     persistent: Optional[bool] = None, delta=None):
+                     persistent: Optional[bool] = None, delta=None, _arm=None):
         """Apply the strata listed in ``seq`` (a permutation of
         range(n_strata) is one epoch; stratum_order draws one) with step
         rotation ``seed``.  ``delta`` = (dQ, db_i)
@@ -1296,20 +1298,23 @@ class SGDEngine:
         seq = (np.arange(pl.n_strata, dtype=np.int32) if seq is None
                else np.ascontiguousarray(seq, np.int32))
         j = self._regroup_pick(seed) if delta is None else 0
+        # a pending beside-mode RMSE pass rides on this epoch's first launch
+        # (_arm: handed down by the engine whose relabelled plan this is)
+        arm = _arm if _arm is not None else (self._beside_armed() if delta is None else None)
         if j > 0:
             return self._epoch_regroup(j - 1, seq, seed, lr, reg, update_user, update_item,
-                                       timing, persistent)
+                                       timing, persistent, arm)
         if isinstance(pl, PhasedStrata):
             return self._epoch_phased(pl, seq, seed, lr, reg, update_user, update_item, timing,
-                                      persistent, delta)
+                                      persistent, delta, arm)
         ms = (ctypes.c_double * 2)() if timing else None
         flags = self._strata_flags(pl, persistent)
         self._run_strata(pl, seq, seed, lr, reg, update_user, update_item, flags, ms, delta,
-                         self.Q, self.bi, self.n_items)
+                         self.Q, self.bi, self.n_items, arm)
         return (ms[0], int(ms[1])) if timing else None
 
     def _epoch_regroup(self, j, seq, seed, lr, reg, update_user, update_item, timing,
-                       persistent):
+                       persistent, arm=None):
         """One epoch on regrouping j: the parameters are gathered into its
         labelling, swept there, and gathered back (device index copies)."""
         e, pu, pi = self._regroups[j]
@@ -1321,7 +1326,8 @@ class SGDEngine:
         self._permute(e, pu, pi, scatter=True)
         self._ensure_strata_ws(e.strata.B, len(seq))
         e._strata_ws = self._strata_ws           # shared counters and error word
-        out = e.epoch_strata(seq, seed, lr, reg, update_user, update_item, timing, persistent)
+        out = e.epoch_strata(seq, seed, lr, reg, update_user, update_item, timing, persistent,
+                             _arm=arm)
         self._permute(e, pu, pi, scatter=False)
         return out
 
@@ -1399,7 +1405,7 @@ class SGDEngine:
         return flags
 
     def _epoch_phased(self, pl, seq, seed, lr, reg, update_user, update_item, timing,
-                      persistent, delta):
+                      persistent, delta, arm=None):
         """The phases of one epoch in order, each on its rows of Q / b_i (and
         of the delta buffers)."""
         flags = self._strata_flags(pl, persistent)
@@ -1408,9 +1414,12 @@ class SGDEngine:
             lo, hi = int(pl.ilo[p]), int(pl.ilo[p + 1])
             ms = (ctypes.c_double * 2)() if timing else None
             d = None if delta is None else (delta[0][lo:hi], delta[1][lo:hi])
+            use = arm if sub.n_positions and len(seq) else None
             self._run_strata(sub, seq, seed, lr, reg, update_user, update_item, flags, ms, d,
                              self.Q[lo:hi], self.bi[lo:hi] if self.bi is not None else None,
-                             hi - lo)
+                             hi - lo, use)
+            if use is not None:
+                arm = None                             # the epoch's first launch carries it
             if timing:
                 tot_ms += ms[0]
                 launches += int(ms[1])
@@ -1439,7 +1448,7 @@ class SGDEngine:
         return (ms[0], int(ms[1])) if timing else None
 
     def _run_strata(self, pl, seq, seed, lr, reg, update_user, update_item, flags, ms, delta,
-                    Q, bi, n_items):
+                    Q, bi, n_items, arm=None):
         self._ensure_strata_ws(pl.B, len(seq))
         args = (_tp(pl.d_u), _tp(pl.d_i), _tp(pl.d_r),
                 pl.n_positions, pl.B, _tp(pl.d_ubnd), _tp(pl.d_ibnd), _tp(pl.d_bstep),
@@ -1450,7 +1459,16 @@ class SGDEngine:
                 self.min_rating, self.max_rating, int(update_user), int(update_item),
                 flags, _tp(self._strata_ws), self._strata_ws.numel() * 4)
         with torch.cuda.device(self.dev):
-            if delta is None:
+            if arm is not None and delta is None and len(seq) and pl.n_positions:
+                # the launch carries the next ticket; whatever it turns out
+                # to be (persistent or not), the same ticket is written
+                # behind it on this stream, and the pending pass is enqueued
+                # on the side stream behind a wait for it
+                arm["ticket"] += 1
+                _lib.call("mf_sgd_epoch_strata_ticket", *args, arm["handle"], arm["ticket"],
+                          None, self.stream, ms)
+                arm["launch"](arm["ticket"])
+            elif delta is None:
                 _lib.call("mf_sgd_epoch_strata", *args, self.stream, ms)
             else:
                 _lib.call("mf_sgd_epoch_strata_delta", *args, _tp(delta[0]), _tp(delta[1]),
@@ -1601,9 +1619,167 @@ class SGDEngine:
                       self.stream, ms)
         return (ms[0], int(ms[1])) if timing else None
 
+    # ------------------------------------------------- RMSE pass beside a sweep
+    # "Beside mode" (DESIGN.md section 5): sse_async() only snapshots the
+    # parameters (one launch) and marks the pass pending; the next
+    # epoch_strata() launches its sweep with a resident ticket and enqueues
+    # the pass -- one workgroup per CU -- on a side stream behind a wait for
+    # that ticket, so it runs beside the sweep's resident grid.  Measured at
+    # C3 (FP64) the sweep stretches by about the time the pass takes alone
+    # (both are bound by the same HBM), so the mode is OFF unless
+    # MF_SSE_BESIDE=1.
+    #
+    # the CU's limits the fit check is asked with (gfx950: 4 SIMDs of 512
+    # registers per lane, 160 KiB of LDS)
+    CU_SIMD_REGS, CU_SIMDS, CU_LDS = 512, 4, 160 << 10
+
+    def _sse_args(self, P, Q, bu, bi):
+        offs = self.eval_offs
+        return (_tp(self.eu), _tp(self.ei), _tp(self.er), self.n, self.global_mean, _tp(bu),
+                _tp(bi), _tp(P), _tp(Q), self.n_users, self.n_items, self.k, self.kcode,
+                self.dcode, self.gamma, self.min_rating, self.max_rating, _np(offs),
+                0 if offs is None else len(offs) - 1)
+
+    def _beside_state(self):
+        """The beside-mode state of this engine (built at first use), or None
+        where the mode cannot apply: no factor model, no strata plan, a
+        multi-GPU run, a plan that does not run persistently, a device without
+        hipStreamWaitValue32, or kernels for which 'exactly one pass workgroup
+        beside a sweep workgroup' (mf_beside_fit) does not hold."""
+        if self._bs is not None:
+            return self._bs or None
+        pl = self.strata
+        if pl is None or self.P is None:       # (not yet: asked again later)
+            return None
+        self._bs = False
+        if self.bias_only or self.n == 0 or getattr(self, "_regroup_of", None) is not None:
+            return None
+        if torch.distributed.is_available() and torch.distributed.is_initialized() \
+                and torch.distributed.get_world_size() > 1:
+            return None
+        sub = next((s for s in (pl.phases if isinstance(pl, PhasedStrata) else [pl])
+                    if s.n_positions), None)
+        if sub is None:
+            return None
+        sweep, apass = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)()
+        with torch.cuda.device(self.dev):
+            if not _lib.load().mf_beside_supported():
+                return None
+            # the kernel the plan's persistent launch runs (no launch)
+            seq = np.arange(sub.n_strata, dtype=np.int32)
+            flags = self._strata_flags(sub, True) | _lib.MF_FLAG_PREPARE
+            self._ensure_strata_ws(sub.B, len(seq))
+            _lib.call("mf_sgd_epoch_strata_ticket", _tp(sub.d_u), _tp(sub.d_i), _tp(sub.d_r),
+                      sub.n_positions, sub.B, _tp(sub.d_ubnd), _tp(sub.d_ibnd), _tp(sub.d_bstep),
+                      sub.NS, sub.max_items, sub.max_users, _np(seq), len(seq), 0,
+                      self.global_mean, None, None, None, None, self.n_users, self.n_items,
+                      self.k, self.kcode, self.dcode, self.gamma, 0.0, 0.0, self.min_rating,
+                      self.max_rating, 1, 1, flags, _tp(self._strata_ws),
+                      self._strata_ws.numel() * 4, None, 0, sweep, self.stream, None)
+            _lib.call("mf_sse_beside", None, 0, *self._sse_args(self.P, self.Q, self.bu, self.bi),
+                      _tp(self.ws), _VOID(self.sse_buf.data_ptr()), self.stream, apass)
+            info = dict(sweep=tuple(sweep), sse=tuple(apass))
+            self.beside_info = info
+            if not sweep[0] or not apass[0] or not _lib.load().mf_beside_fit(
+                    *sweep, *apass, self.CU_SIMD_REGS, self.CU_SIMDS, self.CU_LDS):
+                return None
+            handle = ctypes.c_void_p()
+            try:
+                _lib.call("mf_beside_create", ctypes.byref(handle))
+            except _lib.MFLibraryError:
+                return None
+            self._bs = dict(
+                handle=handle, ticket=0, pending=None, done=None, ready=None,
+                side=torch.cuda.Stream(self.dev), launch=self._beside_launch,
+                P=torch.empty_like(self.P), Q=torch.empty_like(self.Q),
+                bu=torch.empty_like(self.bu), bi=torch.empty_like(self.bi),
+                ws=torch.empty_like(self.ws), **info)
+        return self._bs
+
+    @property
+    def beside_active(self) -> bool:
+        """True when sse_async() defers its pass to run beside the next
+        sweep (MF_SSE_BESIDE=1 and _beside_state() applies)."""
+        return os.environ.get("MF_SSE_BESIDE") == "1" and self._beside_state() is not None
+
+    def _beside_armed(self):
+        """The state whose pending pass the next sweep launch must carry."""
+        bs = self._bs
+        return bs if bs and bs["pending"] is not None else None
+
+    def _beside_snapshot(self, slot: int) -> None:
+        """sse_async() in beside mode: one launch copies the parameters to
+        the snapshot; the pass of ``slot`` is pending from here on."""
+        bs = self._bs
+        main = torch.cuda.current_stream(self.dev)
+        if bs["pending"] is not None:          # no sweep since the last one: it runs now
+            self._beside_flush()
+        if self.sse_buf.numel() < slot + 1:
+            bs["side"].synchronize()           # no pass writes into the old buffer
+            self._ensure_sse_slots(slot + 1)
+        if bs["done"] is not None:
+            main.wait_event(bs["done"])        # the previous pass has read the snapshot
+        names = ("P", "Q", "bu", "bi")
+        dst = (ctypes.c_void_p * 4)(*[bs[x].data_ptr() for x in names])
+        src = (ctypes.c_void_p * 4)(*[getattr(self, x).data_ptr() for x in names])
+        nb = (ctypes.c_int64 * 4)(*[bs[x].numel() * bs[x].element_size() for x in names])
+        with torch.cuda.device(self.dev):
+            _lib.call("mf_copy_arrays", 4, dst, src, nb, self.stream)
+        bs["ready"] = torch.cuda.Event()
+        bs["ready"].record(main)
+        bs["pending"] = slot
+
+    def _beside_launch(self, ticket: int) -> None:
+        """Behind the sweep launch that carries ``ticket``: the pending pass
+        on the side stream, released when that launch's grid is resident (or,
+        at the latest, by the write behind the sweep)."""
+        bs = self._bs
+        side = bs["side"]
+        side.wait_event(bs["ready"])
+        out = _VOID(self.sse_buf.data_ptr() + 8 * bs["pending"])
+        with torch.cuda.device(self.dev):
+            _lib.call("mf_sse_beside", bs["handle"], ticket,
+                      *self._sse_args(bs["P"], bs["Q"], bs["bu"], bs["bi"]), _tp(bs["ws"]), out,
+                      _VOID(side.cuda_stream), None)
+        bs["done"] = torch.cuda.Event()
+        bs["done"].record(side)
+        bs["pending"] = None
+
+    def _beside_flush(self) -> None:
+        """Run a pending pass now, alone, on the launch stream, from the
+        snapshot and with the same grid as beside a sweep (one workgroup per
+        CU), so a slot's bits do not depend on which way its pass ran."""
+        bs = self._bs
+        if not bs or bs["pending"] is None:
+            return
+        main = torch.cuda.current_stream(self.dev)
+        if bs["done"] is not None:
+            main.wait_event(bs["done"])        # (the workspace is the side stream's)
+            bs["done"] = None
+        slot, bs["pending"] = bs["pending"], None
+        self.sse_from(slot, bs["P"], bs["Q"], bs["bu"], bs["bi"], bs["ws"], main,
+                      max_blocks=self._cus())
+
+    def __del__(self):
+        bs = getattr(self, "_bs", None)
+        if not bs or sys.is_finalizing():
+            return
+        try:
+            bs["side"].synchronize()
+            _lib.load().mf_beside_destroy(bs["handle"])
+        except Exception:            # noqa: BLE001 -- never raise from a finaliser
+            pass
+        self._bs = False
+
     # ---------------------------------------------------------- read-only
     def sse_async(self, slot: int) -> None:
-        """Enqueue the training SSE into device slot ``slot``."""
+        """Enqueue the training SSE into device slot ``slot`` (beside mode:
+        snapshot the parameters; the pass runs beside the next sweep, or at
+        sse_values())."""
+        if self.beside_active:
+            self._beside_snapshot(slot)
+            return
+        self._beside_flush()
         self._ensure_sse_slots(slot + 1)
         out = _VOID(self.sse_buf.data_ptr() + 8 * slot)
         with torch.cuda.device(self.dev):
@@ -1687,9 +1863,15 @@ class SGDEngine:
         ov["done"] = done
 
     def sse_join(self) -> None:
-        """Make the main stream wait for an overlapped SSE (sse_overlap)."""
+        """Make the main stream wait for an overlapped SSE (sse_overlap, or
+        beside mode: a still pending pass runs now, a launched one is waited
+        for)."""
         if self._ov is not None and self._ov["done"] is not None:
             torch.cuda.current_stream(self.dev).wait_event(self._ov["done"])
+        if self._bs:
+            self._beside_flush()
+            if self._bs["done"] is not None:
+                torch.cuda.current_stream(self.dev).wait_event(self._bs["done"])
 
     def sse_values(self, n_slots: int) -> np.ndarray:
         self.sse_join()
