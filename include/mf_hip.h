@@ -735,6 +735,85 @@ int mf_cf_predict(const int32_t* entity_ids, const int32_t* other_ids, int64_t n
                   double global_mean, double min_rating, double max_rating,
                   int32_t bound_ratings, double* out, void* stream);
 
+/* ---------------- BPR: Bayesian personalised ranking ---------------------- */
+
+/*
+ * BPRMF (bpr_matrix_factorization.py; Rendle et al. 2009; no counterpart in the
+ * reference).  The data are interaction strengths: the pairs with r > 0 are
+ * the POSITIVES, an observed pair with r = 0 counts as unobserved.  The score
+ * is s(u,i) = x_u . y_i + b_i -- mf_predict's linear kernel with global mean 0
+ * and zero user biases.  One update takes a triple (u, i, j), i a positive of
+ * u and j not; every right-hand side takes the values from before the triple:
+ *     d   = y_i - y_j                       (elementwise)
+ *     z   = x_u . d + (b_i - b_j)
+ *     g   = 1 / (1 + exp(z))
+ *     x_u = x_u + lr (g d - reg x_u)
+ *     y_i = y_i + lr ( g x_u - reg y_i)     b_i = b_i + lr ( g - reg b_i)
+ *     y_j = y_j + lr (-g x_u - reg y_j)     b_j = b_j + lr (-g - reg b_j)
+ * (gradient ascent on ln sigmoid(z) - reg/2 (|x_u|^2 + |y_i|^2 + |y_j|^2 +
+ * b_i^2 + b_j^2)).  FP64 evaluates exactly these expressions, unfused, IEEE
+ * exp and division; only the k-long sum follows the lane group's fixed order.
+ * FP32 uses fused multiply-adds, v_exp_f32 of z log2(e) and v_rcp_f32.
+ *
+ * One EPOCH has one triple per positive.  The visit order is a permutation of
+ * the positives; the triple at visit position t (0-based) takes its negative
+ * from a counter-based generator.  With 64-bit wrap-around arithmetic and
+ *     mix(x):  x ^= x >> 30;  x *= 0xbf58476d1ce4e5b9;  x ^= x >> 27;
+ *              x *= 0x94d049bb133111eb;  x ^= x >> 31        (splitmix64's finaliser)
+ *     base     = mix(seed + (t + 1) * 0x9e3779b97f4a7c15)
+ *     h(a)     = mix(base + (a + 1) * 0xd1b54a32d192ed03)
+ *     j(a)     = ((h(a) >> 32) * n_items) >> 32               (multiply-shift)
+ * the negative is the first j(a), a = 0..15, that is neither i nor in u's
+ * sorted positive list (binary search); if all 16 attempts fail the triple is
+ * SKIPPED: neg = -1, no update, no part in the loss.  The multiply-shift maps
+ * 2^32 values onto n_items: every item has floor or ceil(2^32 / n_items)
+ * preimages, a relative bias of at most n_items / 2^32 (2.4e-4 at 10^6 items).
+ * The generator has no state and uses no atomics: the integers do not depend
+ * on the launch geometry.  The epoch's result is the sequential sweep over the
+ * kept triples in visit order.
+ *
+ * mf_bpr_sample: one thread per visit position.
+ *   order           DEVICE, nullable, n_pos (int32): visit position -> positive
+ *   pos_users/items DEVICE, n_pos: the positives
+ *   user_ptr        DEVICE, n_users + 1 (int64): CSR offsets by user
+ *   user_items      DEVICE, int32: each user's positive items, ascending
+ *   neg_items       DEVICE, n_pos (int32), written: per visit position, -1 = skipped
+ *
+ * mf_bpr_epoch: mf_sgd_epoch's batch contract for triples.  The three id
+ * arrays are DEVICE arrays of n_triples entries (a triple index is whatever
+ * `order` holds, e.g. the visit position); batch_offsets (n_batches + 1) and
+ * batch_seq (nullable) are HOST arrays; order (DEVICE, nullable) lists triple
+ * indices batch by batch -- mf_sched_levels3's output.  One launch per batch;
+ * no two triples of a batch may share a user, or an item in either role.
+ *   item_biases, user_features, item_features   DEVICE, dtype, updated in place
+ *   update_user_params / update_item_params     0: that side is read only
+ *   z_out           DEVICE, dtype, one per schedule position: the triple's
+ *                   pre-update z (the loss is the mean of softplus(-z), the
+ *                   pairwise accuracy the mean of [z > 0])
+ * A listed triple with neg = -1 makes no update and leaves its z_out entry.
+ *
+ * mf_bpr_max_factors(): the largest n_factors mf_bpr_epoch takes (three rows
+ * per triple are held in registers; no instantiation spills, so it equals
+ * mf_max_factors()).
+ *
+ * Both: counts >= 0, dtype MF_F32 or MF_F64, n_factors in [0,
+ * mf_bpr_max_factors()], no NULL for an array that is read or written -- else
+ * MF_ERR_INVALID, before any device work, with the argument's name in
+ * mf_last_error().  n_pos == 0 (n_triples == 0, no batch) returns MF_OK.
+ */
+int32_t mf_bpr_max_factors(void);
+int mf_bpr_sample(const int32_t* order, const int32_t* pos_users, const int32_t* pos_items,
+                  int64_t n_pos, const int64_t* user_ptr, const int32_t* user_items,
+                  int32_t n_users, int32_t n_items, uint64_t seed, int32_t* neg_items,
+                  void* stream);
+int mf_bpr_epoch(const int32_t* user_ids, const int32_t* item_ids, const int32_t* neg_items,
+                 int64_t n_triples, const int32_t* order, const int64_t* batch_offsets,
+                 int32_t n_batches, const int32_t* batch_seq, int32_t n_seq, void* item_biases,
+                 void* user_features, void* item_features, int32_t n_users, int32_t n_items,
+                 int32_t n_factors, int32_t dtype, double lr, double reg,
+                 int32_t update_user_params, int32_t update_item_params, void* z_out,
+                 void* stream);
+
 /* ---------------- multi-GPU replica exchange ----------------------------- */
 
 /*
@@ -801,6 +880,30 @@ int mf_sched_levels_chunked(const int32_t* user_ids, const int32_t* item_ids,
                             int32_t n_items, int32_t use_user, int32_t use_item,
                             int32_t n_chunks, int32_t* sched_out, int64_t* level_offsets,
                             int64_t offsets_cap, int32_t* n_levels_out);
+
+/*
+ * The exact-order schedule for BPR's (user, positive item, negative item)
+ * triples (mf_bpr_epoch).  The three arrays are in VISIT order (triple t is
+ * visit position t).  level(t) = 1 + max(last level of the user, of item i, of
+ * item j); both item roles share one last-level table, so an item that is i in
+ * one triple and j in another conflicts.  use_user / use_item as in
+ * mf_sched_levels (use_item = 0: items frozen, levels by user only).  Triples
+ * with neg = -1 (skipped by the sampler) get no level and are left out;
+ * n_kept_out receives the number listed.  n_chunks as in
+ * mf_sched_levels_chunked: 1 gives the greedy levels, more (<= 0: by size)
+ * level each chunk of visit positions alone and place its levels after the
+ * previous chunk's -- the same sequential sweep, more levels.  Ids outside
+ * [0, n_users) x [0, n_items) x [-1, n_items), and triples with i == j, are
+ * rejected (MF_ERR_INVALID).  n < 2^31.
+ *   sched_out        host, n: the kept visit positions by level, each level
+ *                    in visit order (n_kept entries written)
+ *   level_offsets    host, capacity `offsets_cap` (>= n_levels + 1)
+ */
+int mf_sched_levels3(const int32_t* user_ids, const int32_t* item_ids, const int32_t* neg_ids,
+                     int64_t n, int32_t n_users, int32_t n_items, int32_t use_user,
+                     int32_t use_item, int32_t n_chunks, int32_t* sched_out,
+                     int64_t* level_offsets, int64_t offsets_cap, int32_t* n_levels_out,
+                     int64_t* n_kept_out);
 
 /*
  * Throughput schedule.  Greedy edge colouring of the bipartite rating graph

@@ -259,6 +259,132 @@ extern "C" int mf_sched_levels_chunked(const int32_t* user_ids, const int32_t* i
     return MF_OK;
 }
 
+// Exact order for (user, positive item, negative item) triples (BPR,
+// mf_bpr_epoch): a triple reads and writes its user's row and BOTH item rows,
+// so two triples conflict when they share the user or when any item of one is
+// any item of the other -- one last-level table serves both item roles.  The
+// arrays are in visit order (no separate `order`); triples with neg = -1 were
+// skipped by the sampler and get no level.  Chunks as in
+// mf_sched_levels_chunked: chunk c's triples are levelled alone and its levels
+// follow all of chunk c-1's; its kept triples fill sched_out from the kept
+// count of the chunks before it.
+extern "C" int mf_sched_levels3(const int32_t* user_ids, const int32_t* item_ids,
+                                const int32_t* neg_ids, int64_t n, int32_t n_users,
+                                int32_t n_items, int32_t use_user, int32_t use_item,
+                                int32_t n_chunks, int32_t* sched_out, int64_t* level_offsets,
+                                int64_t offsets_cap, int32_t* n_levels_out,
+                                int64_t* n_kept_out) {
+    if (n < 0 || n >= ((int64_t)1 << 31) || n_users < 0 || n_items < 0 || !n_levels_out ||
+        !n_kept_out || (n > 0 && (!sched_out || !user_ids || !item_ids || !neg_ids)) ||
+        !level_offsets || offsets_cap < 1) {
+        set_error("mf_sched_levels3: bad arguments");
+        return MF_ERR_INVALID;
+    }
+    int T = n_chunks > 0 ? n_chunks : (n >= ((int64_t)1 << 20) ? mf::host_threads() : 1);
+    T = (int)std::max<int64_t>(1, std::min<int64_t>(T, std::max<int64_t>(n, 1)));
+    try {
+        std::vector<int64_t> lo(T + 1);
+        for (int c = 0; c <= T; ++c) lo[c] = n * c / T;
+        auto lvl = mf::big_alloc<int32_t>(n);              // 0 = skipped
+        if (!lvl) throw std::bad_alloc();
+        std::vector<int32_t> depth(T, 0);
+        std::vector<std::vector<int64_t>> cnt(T);
+        std::vector<int64_t> bad(T, -1);                   // first triple with bad ids
+        mf::ThreadErr err;
+        auto pass1 = [&](int c) {
+            err.guard([&]() {
+                std::vector<int32_t> lu(use_user ? (size_t)n_users : 0, 0);
+                std::vector<int32_t> li(use_item ? (size_t)n_items : 0, 0);
+                int32_t maxl = 0;
+                for (int64_t t = lo[c]; t < lo[c + 1]; ++t) {
+                    const int32_t uu = user_ids[t], ii = item_ids[t], jj = neg_ids[t];
+                    if ((uint32_t)uu >= (uint32_t)n_users || (uint32_t)ii >= (uint32_t)n_items ||
+                        jj < -1 || jj >= n_items || jj == ii) {
+                        bad[c] = t;
+                        return;
+                    }
+                    if (jj < 0) {
+                        lvl[t] = 0;
+                        continue;
+                    }
+                    int32_t L = 0;
+                    if (use_user) L = lu[uu];
+                    if (use_item) L = std::max(L, std::max(li[ii], li[jj]));
+                    L += 1;
+                    if (use_user) lu[uu] = L;
+                    if (use_item) li[ii] = li[jj] = L;
+                    lvl[t] = L;
+                    maxl = std::max(maxl, L);
+                }
+                depth[c] = maxl;
+                std::vector<int64_t>& h = cnt[c];
+                h.assign((size_t)maxl + 1, 0);
+                for (int64_t t = lo[c]; t < lo[c + 1]; ++t) ++h[lvl[t]];   // h[0]: skipped
+            });
+        };
+        std::vector<std::thread> th;
+        for (int c = 1; c < T; ++c) th.emplace_back(pass1, c);
+        pass1(0);
+        for (auto& x : th) x.join();
+        th.clear();
+        err.rethrow();
+        for (int c = 0; c < T; ++c) {
+            if (bad[c] >= 0) {
+                const int64_t t = bad[c];
+                set_error("triple %lld has ids (%d, %d, %d) outside [0,%d) x [0,%d) x [-1,%d) "
+                          "or equal items", (long long)t, user_ids[t], item_ids[t], neg_ids[t],
+                          n_users, n_items, n_items);
+                return MF_ERR_INVALID;
+            }
+        }
+        std::vector<int64_t> base(T + 1, 0), first(T + 1, 0);   // levels / kept before chunk c
+        for (int c = 0; c < T; ++c) {
+            base[c + 1] = base[c] + depth[c];
+            first[c + 1] = first[c] + (lo[c + 1] - lo[c]) - cnt[c][0];
+        }
+        const int64_t nl = base[T];
+        *n_levels_out = (int32_t)nl;                       // (nl <= n < 2^31)
+        *n_kept_out = first[T];
+        if (nl + 1 > offsets_cap) {
+            set_error("level_offsets capacity %lld < %lld", (long long)offsets_cap,
+                      (long long)(nl + 1));
+            return MF_ERR_CAPACITY;
+        }
+        level_offsets[0] = 0;
+        for (int c = 0; c < T; ++c) {
+            int64_t acc = first[c];
+            for (int32_t L = 1; L <= depth[c]; ++L) {
+                acc += cnt[c][L];
+                level_offsets[base[c] + L] = acc;
+            }
+        }
+        auto pass2 = [&](int c) {
+            err.guard([&]() {
+                const int32_t D = depth[c];
+                std::vector<int64_t> cur((size_t)D + 1, 0);
+                int64_t acc = first[c];
+                for (int32_t L = 1; L <= D; ++L) {
+                    cur[L] = acc;
+                    acc += cnt[c][L];
+                }
+                for (int64_t t = lo[c]; t < lo[c + 1]; ++t)
+                    if (lvl[t] > 0) sched_out[cur[lvl[t]]++] = (int32_t)t;
+            });
+        };
+        for (int c = 1; c < T; ++c) th.emplace_back(pass2, c);
+        pass2(0);
+        for (auto& x : th) x.join();
+        err.rethrow();
+    } catch (const std::bad_alloc&) {
+        set_error("mf_sched_levels3: out of host memory");
+        return MF_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error("mf_sched_levels3: %s", e.what());
+        return MF_ERR_INVALID;
+    }
+    return MF_OK;
+}
+
 extern "C" int mf_sched_color(const int32_t* user_ids, const int32_t* item_ids, int64_t n,
                               int32_t n_users, int32_t n_items, int32_t* sched_out,
                               int64_t* color_offsets, int64_t offsets_cap,

@@ -9,7 +9,9 @@ train_update_test_split are the host-side surface around them.  ALSMF (no
 reference counterpart: BASELINE config 5) fits the same linear factor model
 by alternating least squares with an MFMA Gramian; ImplicitALSMF (no
 reference counterpart either) fits implicit-feedback strengths by
-confidence-weighted ALS over all user x item pairs.  ItemItemCF and
+confidence-weighted ALS over all user x item pairs; BPRMF (no counterpart
+either) optimises the ranking of each user's positives over the rest by
+exact-order SGD on sampled (user, positive, negative) triples.  ItemItemCF and
 UserUserCF are the reference's neighbourhood models
 (collaborative_filtering.py): a float32 similarity matrix built on the GPU
 from the sparse ratings (mf_cf_stats, mf_cf_similarity) and a
@@ -19,6 +21,7 @@ of the reference is outside this build's scope.
 
 from .als_matrix_factorization import ALSMF
 from .baseline_model import BaselineModel
+from .bpr_matrix_factorization import BPRMF
 from .collaborative_filtering import ItemItemCF, UserUserCF
 from .implicit_als_matrix_factorization import ImplicitALSMF
 from .kernel_matrix_factorization import KernelMF
@@ -27,6 +30,7 @@ from .utils import ranking_metrics_from_ranks, train_update_test_split
 
 __all__ = [
     "ALSMF",
+    "BPRMF",
     "BaselineModel",
     "ImplicitALSMF",
     "ItemItemCF",

@@ -137,6 +137,14 @@ SIGNATURES = {
     "mf_cf_predict": (ctypes.c_int, [
         _P, _P, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32,   # ..., n_ent n_oth dtype nn
         _F64, _F64, _F64, _I32, _P, _P]),                           # mu min max bound out stream
+    "mf_bpr_max_factors": (ctypes.c_int32, []),
+    "mf_bpr_sample": (ctypes.c_int, [
+        _P, _P, _P, _I64, _P, _P, _I32, _I32,         # order, positives, n, CSR, n_users n_items
+        ctypes.c_uint64, _P, _P]),                    # seed, neg_items, stream
+    "mf_bpr_epoch": (ctypes.c_int, [
+        _P, _P, _P, _I64, _P, _P, _I32, _P, _I32,     # triples, n, order, offs, nb, seq, nseq
+        _P, _P, _P, _I32, _I32, _I32, _I32,           # bi, P, Q, n_users n_items k dtype
+        _F64, _F64, _I32, _I32, _P, _P]),             # lr reg upd_u upd_i z_out stream
     "mf_replica_delta": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P]),
     "mf_replica_apply": (ctypes.c_int, [_P, _P, _I64, _I32, _F64, _P]),
     "mf_warmup": (ctypes.c_int, [ctypes.c_int32, _P]),
@@ -145,6 +153,8 @@ SIGNATURES = {
         _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
     "mf_sched_levels_chunked": (ctypes.c_int, [
         _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
+    "mf_sched_levels3": (ctypes.c_int, [
+        _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P, _P]),
     "mf_sched_color": (ctypes.c_int, [
         _P, _P, _I64, _I32, _I32, _P, _P, _I64, _P]),
     "mf_sched_slices": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P]),

@@ -2255,6 +2255,179 @@ class ImplicitALS(FactorALS):
         return float(self.loss_async(alpha, reg).item())
 
 
+def sched_levels3(u: np.ndarray, i: np.ndarray, j: np.ndarray, n_users: int, n_items: int,
+                  use_user: bool = True, use_item: bool = True,
+                  n_chunks: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """Exact-order batches of (user, positive, negative) triples given in visit
+    order (mf_sched_levels3): (the kept visit positions grouped by level, level
+    offsets).  Triples with j = -1 are left out; ``n_chunks`` as in
+    ``sched_levels_chunked`` (1 = the greedy levels)."""
+    n = len(u)
+    u = np.ascontiguousarray(u, np.int32)
+    i = np.ascontiguousarray(i, np.int32)
+    j = np.ascontiguousarray(j, np.int32)
+    if len(i) != n or len(j) != n:
+        raise ValueError("the triple arrays differ in length")
+    sched = np.empty(n, np.int32)
+    offs = np.empty(n + 1, np.int64)
+    nl = ctypes.c_int32(0)
+    kept = ctypes.c_int64(0)
+    _lib.call("mf_sched_levels3", _np(u), _np(i), _np(j), n, n_users, n_items, int(use_user),
+              int(use_item), int(n_chunks), _np(sched), _np(offs), len(offs), ctypes.byref(nl),
+              ctypes.byref(kept))
+    return sched[: kept.value], offs[: nl.value + 1].copy()
+
+
+class BPR:
+    """Bayesian personalised ranking by exact-order SGD (mf_bpr_sample +
+    mf_sched_levels3 + mf_bpr_epoch; include/mf_hip.h, "BPR").  The engine's
+    ratings are interaction strengths: the pairs with r > 0 are the positives,
+    kept on the device with each user's sorted positive list.  The engine must
+    hold linear-kernel parameters, global_mean 0 and zero user biases, so
+    predict / topk / rank score x_u . y_i + b_i.
+
+    One epoch: ``np.random.shuffle`` of the visit order (the exact schedule's
+    shuffler), one 64-bit seed from the global RandomState, the negatives
+    sampled on the GPU and read back, the levels built on the host, the
+    schedule uploaded, one launch per level.  ``record = True`` keeps every
+    epoch's triples for ``serial_triples`` (else only the last epoch's)."""
+
+    def __init__(self, engine: SGDEngine):
+        e = engine
+        if e.bias_only or e.kernel != "linear":
+            raise ValueError("BPR runs on linear-kernel factor parameters")
+        if e.global_mean != 0.0:
+            raise ValueError("BPR has no global mean (engine.global_mean must be 0)")
+        if e.bu is None or e.bi is None or e.P is None or e.Q is None:
+            raise ValueError("BPR needs the engine's parameters loaded")
+        if bool(torch.any(e.bu != 0)):
+            raise ValueError("BPR has no user biases (engine user biases must be zero)")
+        kmax = _lib.load().mf_bpr_max_factors()
+        if not 0 <= e.k <= kmax:
+            raise ValueError(f"BPR needs 0 <= n_factors <= {kmax}, got {e.k}")
+        self.e = e
+        pos = np.flatnonzero(e.r_host > 0)
+        self.pu = np.ascontiguousarray(e.u_host[pos])
+        self.pi = np.ascontiguousarray(e.i_host[pos])
+        self.n = len(pos)
+        if self.n >= (1 << 31):
+            raise ValueError("BPR takes fewer than 2^31 positives")
+        by_user = np.lexsort((self.pi, self.pu))
+        ptr = np.zeros(e.n_users + 1, np.int64)
+        np.cumsum(np.bincount(self.pu, minlength=e.n_users), out=ptr[1:])
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(e.dev)  # noqa: E731
+        self.pu_d, self.pi_d = to(self.pu), to(self.pi)
+        self.ptr_d, self.ids_d = to(ptr), to(self.pi[by_user])
+        m = max(self.n, 1)
+        self.order = np.arange(self.n, dtype=np.int32)       # shuffled in place every epoch
+        self.order_d = torch.empty(m, dtype=torch.int32, device=e.dev)
+        self.neg_d = torch.empty(m, dtype=torch.int32, device=e.dev)
+        self.sched_d = torch.empty(m, dtype=torch.int32, device=e.dev)
+        self.z = torch.empty(m, dtype=e.tdt, device=e.dev)
+        self.record = False
+        self._triples = {}                                   # epoch -> (u, i, j) in visit order
+        self.tu_d = self.ti_d = None                         # the sampled epoch's users / positives
+        self.epochs_run = 0
+        self.n_levels = 0                                    # of the last epoch
+        self.last_sched = np.zeros(0, np.int32)              # ... its schedule (visit positions)
+
+    def draw(self):
+        """The epoch's two draws from the global RandomState, in order: the
+        shuffle of the visit order, then the 64-bit seed."""
+        _prep.legacy_shuffle_(self.order)                    # = np.random.shuffle(order)
+        return int(np.random.randint(0, 2 ** 64, dtype=np.uint64))
+
+    def sample(self, seed: int) -> None:
+        """Upload the visit order, gather the positives into it (the triple
+        index of mf_bpr_epoch and mf_sched_levels3 is the visit position) and
+        sample the negatives (mf_bpr_sample)."""
+        e = self.e
+        with torch.cuda.device(e.dev):
+            self.order_d[: self.n].copy_(torch.from_numpy(self.order))
+            vis = self.order_d[: self.n].long()
+            self.tu_d = self.pu_d.index_select(0, vis)
+            self.ti_d = self.pi_d.index_select(0, vis)
+            _lib.call("mf_bpr_sample", _tp(self.order_d), _tp(self.pu_d), _tp(self.pi_d), self.n,
+                      _tp(self.ptr_d), _tp(self.ids_d), e.n_users, e.n_items,
+                      ctypes.c_uint64(seed), _tp(self.neg_d), e.stream)
+
+    def readback(self):
+        """The sampled epoch's triples (u, i, j) in visit order on the host,
+        skipped ones (j = -1) included."""
+        return (self.tu_d.cpu().numpy(), self.ti_d.cpu().numpy(),
+                self.neg_d[: self.n].cpu().numpy())
+
+    def levels(self, triples, update_user: bool, update_item: bool, n_chunks: int = 0):
+        """(schedule, level offsets) of the triples (mf_sched_levels3)."""
+        e = self.e
+        return sched_levels3(*triples, e.n_users, e.n_items, update_user, update_item, n_chunks)
+
+    def launch(self, sched: np.ndarray, offs: np.ndarray, lr: float, reg: float,
+               update_user: bool, update_item: bool) -> int:
+        """Upload the schedule and run its levels; the pre-update z of schedule
+        position s is left in ``self.z[s]``.  Returns the number of triples."""
+        kept = self.upload(sched)
+        self.run_levels(offs, lr, reg, update_user, update_item)
+        return kept
+
+    def upload(self, sched: np.ndarray) -> int:
+        kept = len(sched)
+        if kept:
+            with torch.cuda.device(self.e.dev):
+                self.sched_d[:kept].copy_(torch.from_numpy(sched))
+        return kept
+
+    def run_levels(self, offs: np.ndarray, lr: float, reg: float, update_user: bool,
+                   update_item: bool) -> None:
+        """One mf_bpr_epoch call: a launch per level of the uploaded schedule."""
+        e = self.e
+        with torch.cuda.device(e.dev):
+            _lib.call("mf_bpr_epoch", _tp(self.tu_d), _tp(self.ti_d), _tp(self.neg_d), self.n,
+                      _tp(self.sched_d), _np(offs), len(offs) - 1, None, 0, _tp(e.bi),
+                      _tp(e.P), _tp(e.Q), e.n_users, e.n_items, e.k, e.dcode, float(lr),
+                      float(reg), int(update_user), int(update_item), _tp(self.z), e.stream)
+
+    def stats_async(self, kept: int):
+        """(mean softplus(-z), mean [z > 0]) over the last epoch's kept triples
+        as device scalars, reduced in FP64; NaN when nothing was kept."""
+        e = self.e
+        with torch.cuda.device(e.dev):
+            if kept == 0:
+                nan = torch.full((), float("nan"), dtype=torch.float64, device=e.dev)
+                return nan, nan
+            z = self.z[:kept].double()
+            return (torch.mean(torch.logaddexp(torch.zeros_like(z), -z)),
+                    torch.mean((z > 0).double()))
+
+    def epoch(self, lr: float, reg: float, update_user: bool = True, update_item: bool = True,
+              n_chunks: int = 0):
+        """One epoch; returns (loss, pairwise accuracy) as device scalars."""
+        seed = self.draw()
+        if self.n == 0:
+            self.epochs_run += 1
+            return self.stats_async(0)
+        self.sample(seed)
+        triples = self.readback()
+        sched, offs = self.levels(triples, update_user, update_item, n_chunks)
+        kept = self.launch(sched, offs, lr, reg, update_user, update_item)
+        if not self.record:
+            self._triples.clear()
+        self._triples[self.epochs_run] = triples
+        self.epochs_run += 1
+        self.n_levels = len(offs) - 1
+        self.last_sched = sched
+        return self.stats_async(kept)
+
+    def serial_triples(self, epoch: int):
+        """The kept (u, i, j) of epoch ``epoch`` (0-based) in visit order: the
+        sequential sweep the epoch equals."""
+        if epoch not in self._triples:
+            raise KeyError(f"epoch {epoch} was not recorded (set record = True before the epochs)")
+        tu, ti, tj = self._triples[epoch]
+        keep = tj >= 0
+        return tu[keep], ti[keep], tj[keep]
+
+
 class _ErrorPoll:
     """Non-blocking look at the persistent sweep's sticky error word: after
     each epoch's launch a copy of the word goes to pinned host memory behind
