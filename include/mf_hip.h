@@ -331,6 +331,41 @@ int mf_sse_capped(const int32_t* user_ids, const int32_t* item_ids,
                   int32_t max_blocks, double* sse_out, void* stream);
 
 /*
+ * The same sum with the ITEM rows stationary in LDS (k_sse_slab; DESIGN.md
+ * section 5, "Item-stationary RMSE pass").  The ratings are ordered by (item
+ * group, user), users ascending: item group g of n_groups holds the items i
+ * with i * n_groups / n_items == g (mf_sched_tiles(1, n_groups)'s slices).
+ * group_tab (DEVICE, n_groups x (n_windows + 1) int64): the first rating of
+ * group g whose user is >= user boundary w of n_windows user super-windows
+ * (any ascending boundaries; entry n_windows is the group's end).  One
+ * workgroup per group keeps the group's item rows (items_per_group rows of
+ * row_stride >= n_factors values) and biases in LDS; one launch per phase of
+ * min(CUs, max_blocks or all, n_groups) groups and per window, on `stream`.
+ * Every rating's error has mf_sse's bits; the FP64 sum is taken in another,
+ * fixed order (deterministic).  user_features must be below 4 GiB.
+ * attrs_out (nullable, int32[3]): no launch, the kernel as {registers per
+ * thread, waves per workgroup, LDS bytes}.
+ *
+ * mf_sse_slab_plan (host arithmetic only): the smallest n_groups that is a
+ * multiple of n_workgroups and whose largest group fits lds_budget bytes
+ * (<= 0: all of a CU's LDS the kernel may use), rows padded by pad_values
+ * (<= 0: none).  Returns 1 and plan_out = {items_per_group, n_groups, phases,
+ * LDS bytes, row_stride}, or 0 where not even one row fits.
+ */
+size_t mf_sse_slab_workspace_bytes(int32_t n_groups);
+int mf_sse_slab_plan(int32_t n_items, int32_t n_factors, int32_t dtype, int32_t n_workgroups,
+                     int32_t lds_budget, int32_t pad_values, int32_t* plan_out);
+int mf_sse_slab(const int32_t* user_ids, const int32_t* item_ids, const void* ratings,
+                int64_t n_ratings, double global_mean, const void* user_biases,
+                const void* item_biases, const void* user_features,
+                const void* item_features, int32_t n_users, int32_t n_items,
+                int32_t n_factors, int32_t kernel, int32_t dtype, double gamma,
+                double min_rating, double max_rating, const int64_t* group_tab,
+                int32_t n_groups, int32_t n_windows, int32_t items_per_group,
+                int32_t row_stride, void* workspace, int32_t max_blocks, double* sse_out,
+                void* stream, int32_t* attrs_out);
+
+/*
  * The RMSE pass of epoch e beside the persistent sweep of epoch e + 1
  * (off unless the engine is asked, MF_SSE_BESIDE=1).
  *

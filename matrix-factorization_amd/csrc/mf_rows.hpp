@@ -17,6 +17,8 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "mf_common.hpp"
@@ -1089,6 +1091,221 @@ __global__ __launch_bounds__(kBlock) void k_sse_pipe(ReadArgs<T> A, SliceTab SL)
     }
 }
 
+// Training SSE with the ITEM rows stationary in LDS and the user rows
+// gathered ("Item-stationary RMSE pass").  The ratings
+// are ordered by (item group, user); item group g is the contiguous item
+// range [ceil(g ni / G), ceil((g + 1) ni / G)), the items i with
+// floor(i G / ni) == g.  One launch covers one phase (the groups
+// phase * gridDim.x + blockIdx.x) and one user super-window: workgroup b
+// stages its group's item rows and item biases in LDS and walks the ratings
+// [tab[g][w], tab[g][w + 1]) in chunks of 64 (lane j <-> rating j), chunk c
+// by wave c mod waves, so the waves of a workgroup -- and, launch by launch,
+// all workgroups -- move through the users together and a user row is
+// fetched from memory about once per XCD and phase.  Per rating the
+// arithmetic is sse_lean_range's (same lane-to-column layout, the same
+// products, group sum, prediction and FP64 square-add), so every rating's
+// error has the same bits; only the order of the FP64 sum differs.
+//
+// The user rows of a step (S R ratings) are issued NS - 1 steps ahead of
+// their use (NS register sets used in turn; the chunk's triples arrive two
+// chunks ahead, its user biases one).  No workgroup waits on another:
+// workgroup b adds each launch's sum to partials[b] with a plain load and
+// store (the same index owns the word in every launch of the pass, in stream
+// order), and k_sum_partials adds the words in a fixed order.
+struct SlabGeom {
+    const int64_t* tab;      // device: n_groups x (n_windows + 1) rating offsets
+    int32_t n_groups, n_windows;
+    int32_t n_items;
+    int32_t nit;             // LDS rows (>= the items of the largest group)
+    int32_t ks;              // LDS row stride in values (>= k)
+    int32_t phase, window;   // this launch
+    int32_t first;           // 1: partials are written, 0: added to
+};
+
+constexpr int kSlabMaxWaves = 16;
+constexpr int kSlabScratch = 256;      // static LDS beside the slab (the reduction words)
+constexpr int kSlabLdsLimit = 160 * 1024;   // gfx950 LDS per CU (= mf_strata.hpp's kLdsLimit)
+
+template <typename F, int... J>
+__device__ __forceinline__ void static_steps(F&& f, std::integer_sequence<int, J...>) {
+    (f(std::integral_constant<int, J>{}), ...);
+}
+
+template <typename T, int W, int GS, int V, int KERN, int S, int NSETS, int TH>
+__global__ __launch_bounds__(TH) void k_sse_slab(ReadArgs<T> A, SlabGeom B) {
+    using VT = typename VecOf<T, W>::type;
+    constexpr int R = kWave / GS;
+    constexpr int STEP = S * R;
+    static_assert(kWave % STEP == 0, "a chunk of 64 ratings is whole steps");
+    constexpr int Q = kWave / STEP;                 // steps per chunk
+    constexpr int NS = NSETS < Q ? NSETS : Q;       // register sets in turn
+    static_assert(Q % NS == 0, "a chunk is whole turns of the sets");
+    constexpr int NWV = TH / kWave;
+    static_assert(NWV <= kSlabMaxWaves, "reduction words");
+    extern __shared__ __align__(16) unsigned char slab_smem[];
+    __shared__ double red[kSlabMaxWaves];
+    T* const Qs = reinterpret_cast<T*>(slab_smem);
+    T* const Bis = Qs + (size_t)B.nit * B.ks;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const int g = lane / GS;
+    const int l = lane % GS;
+    const int k = A.k;
+    const int kv = k / W;
+    const int ks = B.ks;
+    const Hyper<T> h = A.h;
+    const int64_t grp = (int64_t)B.phase * gridDim.x + blockIdx.x;
+    int64_t a = 0, b = 0;
+    int ilo = 0, nqi = 0;
+    if (grp < B.n_groups) {
+        const int64_t* row = B.tab + grp * (B.n_windows + 1) + B.window;
+        a = min(max(row[0], (int64_t)0), A.n);
+        b = min(max(row[1], a), A.n);
+        const int64_t G = B.n_groups;
+        ilo = (int)((grp * B.n_items + G - 1) / G);
+        const int ihi = (int)(((grp + 1) * B.n_items + G - 1) / G);
+        nqi = min(ihi - ilo, B.nit);
+    }
+    double acc = 0.0;
+    if (a < b && nqi > 0) {                          // (workgroup-uniform)
+        {   // the group's item rows and biases -> LDS
+            const VT* src = reinterpret_cast<const VT*>(A.Q + (int64_t)ilo * k);
+            VT* dst = reinterpret_cast<VT*>(Qs);
+            const int ksv = ks / W, nv = nqi * kv;
+            if (ksv == kv) {
+#pragma unroll 4
+                for (int t = threadIdx.x; t < nv; t += TH) dst[t] = src[t];
+            } else {
+#pragma unroll 4
+                for (int t = threadIdx.x; t < nv; t += TH) {
+                    const int r = t / kv;
+                    dst[r * ksv + (t - r * kv)] = src[t];
+                }
+            }
+            if constexpr (KERN != MF_RBF)
+                for (int t = threadIdx.x; t < nqi; t += TH) Bis[t] = A.Bi[ilo + t];
+        }
+        __syncthreads();
+        const __amdgpu_buffer_rsrc_t rp = buf_rsrc(A.P, A.p_bytes);
+        const __amdgpu_buffer_rsrc_t rbu = buf_rsrc(A.Bu, A.bu_bytes);
+        const uint32_t kb = (uint32_t)k * (uint32_t)sizeof(T);
+        const bool lead = l == 0;
+        const int64_t nch = (b - a + kWave - 1) / kWave;         // chunks of this cell
+        struct Tri { int u, i; T r, bu; };
+        struct Set {
+            VT p[S][V];
+            T rr[S], bu[S];
+            int il[S];
+        };
+        // the triples of chunk c, one rating per lane (past the cell: its last rating)
+        auto fetch = [&](int64_t c, Tri& t) __attribute__((always_inline)) {
+            const int64_t j = min(a + c * kWave + lane, b - 1);
+            t.u = A.u[j]; t.i = A.i[j]; t.r = A.r[j];
+        };
+        auto fetch_bu = [&](Tri& t) __attribute__((always_inline)) {
+            if constexpr (KERN != MF_RBF)
+                t.bu = buf_ld<0, T>(rbu, (uint32_t)t.u * (uint32_t)sizeof(T));
+            else
+                t.bu = (T)0;
+        };
+        auto live_of = [&](int64_t c) __attribute__((always_inline)) -> int {
+            return c < nch ? (int)min((int64_t)kWave, b - (a + c * kWave)) : 0;
+        };
+        auto walk = [&](auto full) __attribute__((always_inline)) {
+            constexpr bool FULL = decltype(full)::value;
+            // issue the user-row loads of the step at chunk offset t
+            auto issue = [&](const Tri& tr, int t, Set& o) __attribute__((always_inline)) {
+#pragma unroll
+                for (int x = 0; x < S; ++x) {
+                    const int src = t + x * R + g;
+                    const int uu = take_i<GS>(tr.u, src);
+                    const int ii = take_i<GS>(tr.i, src);
+                    o.rr[x] = take_f<GS>(tr.r, src);
+                    o.bu[x] = KERN != MF_RBF ? take_f<GS>(tr.bu, src) : (T)0;
+                    // the row inside the slab (clamped: never past the LDS image)
+                    o.il[x] = (int)min((uint32_t)(ii - ilo), (uint32_t)(nqi - 1));
+                    const uint32_t base = (uint32_t)uu * kb;
+#pragma unroll
+                    for (int v = 0; v < V; ++v) {
+                        const int vi = v * GS + l;
+                        const int vc = FULL || vi < kv ? vi : kv - 1;
+                        o.p[x][v] = buf_ld<0, VT>(rp, base + (uint32_t)(vc * W) * (uint32_t)sizeof(T));
+                    }
+                }
+            };
+            auto consume = [&](const Set& o, int t, int nw) __attribute__((always_inline)) {
+#pragma unroll
+                for (int x = 0; x < S; ++x) {
+                    const T* qrow = Qs + o.il[x] * ks;
+                    T part = (T)0;
+#pragma unroll
+                    for (int v = 0; v < V; ++v) {
+                        const int vi = v * GS + l;
+                        const int vc = FULL || vi < kv ? vi : kv - 1;
+                        VT pv[1] = {o.p[x][v]};
+                        VT qv[1] = {*reinterpret_cast<const VT*>(qrow + vc * W)};
+                        const T pt = lane_partial_first<T, W, KERN>(pv, qv);
+                        const T ptm = FULL || vi < kv ? pt : (T)0;
+                        part = v == 0 ? ptm : part + ptm;
+                    }
+                    T bi = (T)0;
+                    if constexpr (KERN != MF_RBF) bi = Bis[o.il[x]];
+                    const T sm = group_sum<GS>(part);
+                    const T err = o.rr[x] - predict_one<T, KERN>(sm, o.bu[x], bi, h);
+                    const bool on = (t + x * R + g < nw) & lead;
+                    const T e = on ? err : (T)0;
+                    if constexpr (std::is_same<T, float>::value)
+                        acc = __builtin_fma((double)e, (double)e, acc);     // e^2 exact in FP64
+                    else
+                        acc += (double)e * (double)e;
+                }
+            };
+            int64_t c = wave;
+            if (c >= nch) return;
+            Tri cur, nxt, nn;
+            Set st[NS];
+            fetch(c, cur);
+            fetch(c + NWV, nxt);
+            fetch_bu(cur);
+            {
+                const int nw0 = live_of(c);
+                static_steps([&](auto jc) __attribute__((always_inline)) {
+                    constexpr int j = decltype(jc)::value;
+                    if (j * STEP < nw0) issue(cur, j * STEP, st[j]);
+                }, std::make_integer_sequence<int, NS - 1>{});
+            }
+            for (; c < nch; c += NWV) {
+                fetch(c + 2 * NWV, nn);
+                fetch_bu(nxt);
+                const int nw = live_of(c), nwn = live_of(c + NWV);
+                static_steps([&](auto jc) __attribute__((always_inline)) {
+                    constexpr int j = decltype(jc)::value;
+                    constexpr int ja = j + NS - 1;            // the step issued now
+                    if constexpr (ja < Q) {
+                        if (ja * STEP < nw) issue(cur, ja * STEP, st[ja % NS]);
+                    } else {
+                        if ((ja - Q) * STEP < nwn) issue(nxt, (ja - Q) * STEP, st[ja % NS]);
+                    }
+                    if (j * STEP < nw) consume(st[j % NS], j * STEP, nw);
+                }, std::make_integer_sequence<int, Q>{});
+                cur = nxt;
+                nxt = nn;
+            }
+        };
+        if (kv == GS * V) walk(std::true_type{});
+        else walk(std::false_type{});
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) t += red[w];
+        A.partials[blockIdx.x] = B.first ? t : A.partials[blockIdx.x] + t;
+    }
+}
+
 __global__ void k_sum_partials(const double* part, int n, double* out);
 
 constexpr int kSseMaxBlocks = 8192;
@@ -1399,7 +1616,106 @@ struct SseRun {
     }
 };
 
+// The item-stationary pass (k_sse_slab): one launch per phase and user
+// super-window on p.stream, then k_sum_partials.  Default: 8 waves per
+// workgroup, two register sets (user rows one step ahead).  The rank-64
+// linear layouts also carry the probe forms MF_SSE_SLAB_WAVES = 4 / 8 / 16
+// and MF_SSE_SLAB_SETS = 1 / 2 / 4 (tools/sse_slab_probe.py).
+struct SseSlabParams {
+    SseParams s;             // (s.S unused)
+    SlabGeom g;              // (phase / window / first set per launch)
+};
+
+template <typename T>
+struct SseSlabRun {
+    const SseSlabParams& q;
+
+    template <int W, int GS, int V, int KERN>
+    int run() {
+        constexpr int S = SlotsFor<kWave / GS, V, W>::S;
+        int waves = 8, sets = 2;
+        if constexpr (KERN == MF_LINEAR && W > 1 && GS == 16 &&
+                      V == (std::is_same<T, double>::value ? 2 : 1)) {
+            if (const char* e = std::getenv("MF_SSE_SLAB_WAVES")) waves = std::atoi(e);
+            if (const char* e = std::getenv("MF_SSE_SLAB_SETS")) sets = std::atoi(e);
+            if (waves == 4 && sets == 1) return go<W, GS, V, KERN, S, 1, 256>(0);
+            if (waves == 4 && sets == 2) return go<W, GS, V, KERN, S, 2, 256>(1);
+            if (waves == 4 && sets == 4) return go<W, GS, V, KERN, S, 4, 256>(2);
+            if (waves == 8 && sets == 1) return go<W, GS, V, KERN, S, 1, 512>(3);
+            if (waves == 8 && sets == 4) return go<W, GS, V, KERN, S, 4, 512>(4);
+            if (waves == 16 && sets == 1) return go<W, GS, V, KERN, S, 1, 1024>(5);
+            if (waves == 16 && sets == 2) return go<W, GS, V, KERN, S, 2, 1024>(6);
+            if (!(waves == 8 && sets == 2)) {
+                set_error("mf_sse_slab: no kernel for %d waves, %d register sets", waves, sets);
+                return MF_ERR_INVALID;
+            }
+        }
+        return go<W, GS, V, KERN, S, 2, 512>(7);
+    }
+
+    template <int W, int GS, int V, int KERN, int S, int NSETS, int TH>
+    int go(int var) {
+        const SseParams& p = q.s;
+        ReadArgs<T> a;
+        a.u = p.u; a.i = p.i; a.r = static_cast<const T*>(p.r);
+        a.P = static_cast<const T*>(p.P); a.Q = static_cast<const T*>(p.Q);
+        a.Bu = static_cast<const T*>(p.bu); a.Bi = static_cast<const T*>(p.bi);
+        a.n = p.n; a.k = p.k; a.bound = 0; a.out = nullptr; a.partials = p.partials;
+        a.h = make_hyper<T>(p.mu, 0.0, 0.0, p.gamma, p.lo, p.hi);
+        a.p_bytes = (uint64_t)p.n_users * p.k * sizeof(T);
+        a.q_bytes = (uint64_t)p.n_items * p.k * sizeof(T);
+        a.bu_bytes = (uint64_t)p.n_users * sizeof(T);
+        a.bi_bytes = (uint64_t)p.n_items * sizeof(T);
+        if (W > 1 && q.g.ks % W != 0) {
+            set_error("mf_sse_slab: row stride %d is not a multiple of %d values", q.g.ks, W);
+            return MF_ERR_INVALID;
+        }
+        auto kfn = k_sse_slab<T, W, GS, V, KERN, S, NSETS, TH>;
+        const size_t lds = ((size_t)q.g.nit * q.g.ks + (size_t)q.g.nit) * sizeof(T);
+        if (p.attrs_out) {
+            hipFuncAttributes fa;
+            MF_HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kfn)));
+            p.attrs_out[0] = fa.numRegs;
+            p.attrs_out[1] = TH / kWave;
+            p.attrs_out[2] = (int32_t)(fa.sharedSizeBytes + lds);
+            return MF_OK;
+        }
+        if (lds > (size_t)(kSlabLdsLimit - kSlabScratch)) {
+            set_error("mf_sse_slab: the slab needs %zu B of LDS (> %d)", lds,
+                      kSlabLdsLimit - kSlabScratch);
+            return MF_ERR_INVALID;
+        }
+        static bool lds_set[8] = {false, false, false, false, false, false, false, false};
+        if (!lds_set[var]) {                          // per instantiation and form
+            MF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             kSlabLdsLimit - kSlabScratch));
+            lds_set[var] = true;
+        }
+        int dev = 0, cus = 0;
+        MF_HIP_CHECK(hipGetDevice(&dev));
+        MF_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        int blocks = std::max(1, std::min(cus, kSseMaxBlocks));
+        if (p.max_blocks > 0) blocks = std::min(blocks, p.max_blocks);
+        blocks = std::min(blocks, q.g.n_groups);
+        const int phases = (q.g.n_groups + blocks - 1) / blocks;
+        SlabGeom gm = q.g;
+        for (int ph = 0; ph < phases; ++ph) {
+            for (int w = 0; w < gm.n_windows; ++w) {
+                gm.phase = ph; gm.window = w; gm.first = ph == 0 && w == 0;
+                hipLaunchKernelGGL(kfn, dim3(blocks), dim3(TH), lds, p.stream, a, gm);
+            }
+        }
+        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(kBlock), 0, p.stream,
+                           (const double*)p.partials, blocks, p.sse_out);
+        MF_HIP_CHECK(hipGetLastError());
+        return MF_OK;
+    }
+};
+
 // defined in mf_rows_f32.hip / mf_rows_f64.hip
+int sse_slab_launch_f32(const SseSlabParams& p);
+int sse_slab_launch_f64(const SseSlabParams& p);
 int sgd_launch_f32(const SgdParams& p);
 int sgd_launch_f64(const SgdParams& p);
 int sse_launch_f32(const SseParams& p);

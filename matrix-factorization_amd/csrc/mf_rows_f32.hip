@@ -14,6 +14,11 @@ int sse_launch_f32(const SseParams& p) {
     return dispatch_rows<float>(p.k, p.kernel, r);
 }
 
+int sse_slab_launch_f32(const SseSlabParams& p) {
+    SseSlabRun<float> r{p};
+    return dispatch_rows<float>(p.s.k, p.s.kernel, r);
+}
+
 
 void touch_rows_f32(hipStream_t s) { hipLaunchKernelGGL(k_touch<1>, dim3(1), dim3(64), 0, s); }
 

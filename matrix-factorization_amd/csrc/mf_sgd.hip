@@ -545,6 +545,92 @@ extern "C" int mf_sse_capped(const int32_t* user_ids, const int32_t* item_ids,
 }
 
 // ---------------------------------------------------------------------------
+// The item-stationary RMSE pass (k_sse_slab).
+static_assert(kSlabLdsLimit == kLdsLimit, "one LDS size");
+
+extern "C" size_t mf_sse_slab_workspace_bytes(int32_t n_groups) {
+    (void)n_groups;                     // one partial per workgroup, at most kSseMaxBlocks
+    return sizeof(double) * (size_t)kSseMaxBlocks;
+}
+
+extern "C" int mf_sse_slab_plan(int32_t n_items, int32_t n_factors, int32_t dtype,
+                                int32_t n_workgroups, int32_t lds_budget, int32_t pad_values,
+                                int32_t* plan_out) {
+    if (plan_out) plan_out[0] = plan_out[1] = plan_out[2] = plan_out[3] = plan_out[4] = 0;
+    const int64_t sz = dtype == MF_F32 ? 4 : dtype == MF_F64 ? 8 : 0;
+    if (!plan_out || sz == 0 || n_items < 1 || n_factors < 1 || n_factors > kMaxFactors ||
+        n_workgroups < 1)
+        return 0;
+    const int64_t limit = kSlabLdsLimit - kSlabScratch;
+    const int64_t budget = lds_budget > 0 ? std::min<int64_t>(lds_budget, limit) : limit;
+    // rows moved 16 B per lane keep a 16-B aligned stride
+    const int64_t wv = 16 / sz;
+    int64_t pad = pad_values > 0 ? pad_values : 0;
+    if (n_factors % wv == 0) pad = (pad + wv - 1) / wv * wv;
+    const int64_t ks = n_factors + pad;
+    const int64_t per_item = (ks + 1) * sz;              // the row and its bias
+    if (per_item > budget) return 0;
+    const int64_t fit = budget / per_item;               // items the budget holds
+    // the smallest multiple of the workgroup count with ceil(ni / G) <= fit
+    const int64_t need = ((int64_t)n_items + fit - 1) / fit;
+    const int64_t G = (need + n_workgroups - 1) / n_workgroups * n_workgroups;
+    if (G > (int64_t)1 << 24) return 0;
+    const int64_t nit = ((int64_t)n_items + G - 1) / G;
+    plan_out[0] = (int32_t)nit;
+    plan_out[1] = (int32_t)G;
+    plan_out[2] = (int32_t)(G / n_workgroups);
+    plan_out[3] = (int32_t)(nit * per_item);
+    plan_out[4] = (int32_t)ks;
+    return 1;
+}
+
+extern "C" int mf_sse_slab(const int32_t* user_ids, const int32_t* item_ids, const void* ratings,
+                           int64_t n_ratings, double global_mean, const void* user_biases,
+                           const void* item_biases, const void* user_features,
+                           const void* item_features, int32_t n_users, int32_t n_items,
+                           int32_t n_factors, int32_t kernel, int32_t dtype, double gamma,
+                           double min_rating, double max_rating, const int64_t* group_tab,
+                           int32_t n_groups, int32_t n_windows, int32_t items_per_group,
+                           int32_t row_stride, void* workspace, int32_t max_blocks,
+                           double* sse_out, void* stream, int32_t* attrs_out) {
+    if (attrs_out) attrs_out[0] = attrs_out[1] = attrs_out[2] = 0;
+    if (n_ratings < 0 || !sse_out || !workspace || n_users < 0 || n_items < 1 || !group_tab ||
+        n_groups < 1 || n_windows < 1 || max_blocks < 0) {
+        set_error("mf_sse_slab: bad arguments");
+        return MF_ERR_INVALID;
+    }
+    const int64_t sz = dtype == MF_F32 ? 4 : 8;
+    if (n_factors < 1 || row_stride < n_factors || items_per_group < 1 ||
+        (int64_t)items_per_group * n_groups < n_items ||
+        ((int64_t)row_stride + 1) * items_per_group * sz > kSlabLdsLimit - kSlabScratch) {
+        set_error("mf_sse_slab: %d groups of %d rows (stride %d) do not hold %d items of rank %d "
+                  "in LDS (mf_sse_slab_plan)", n_groups, items_per_group, row_stride, n_items,
+                  n_factors);
+        return MF_ERR_INVALID;
+    }
+    if ((uint64_t)n_users * (uint64_t)n_factors * (uint64_t)sz >= (1ull << 32) - 64) {
+        set_error("mf_sse_slab: user_features must be below 4 GiB (buffer loads)");
+        return MF_ERR_INVALID;
+    }
+    if (n_ratings == 0) {
+        if (!attrs_out)
+            MF_HIP_CHECK(hipMemsetAsync(sse_out, 0, sizeof(double), (hipStream_t)stream));
+        return MF_OK;
+    }
+    SseSlabParams P{{user_ids, item_ids, ratings, n_ratings, global_mean, user_biases,
+                     item_biases, user_features, item_features, n_users, n_items, n_factors,
+                     kernel, gamma, min_rating, max_rating, (double*)workspace, sse_out,
+                     (hipStream_t)stream, SliceTab{}, max_blocks},
+                    SlabGeom{group_tab, n_groups, n_windows, n_items, items_per_group,
+                             row_stride, 0, 0, 0}};
+    P.s.attrs_out = attrs_out;
+    if (dtype == MF_F32) return sse_slab_launch_f32(P);
+    if (dtype == MF_F64) return sse_slab_launch_f64(P);
+    set_error("unknown dtype code %d", dtype);
+    return MF_ERR_INVALID;
+}
+
+// ---------------------------------------------------------------------------
 // The RMSE pass beside the next epoch's persistent sweep.
 extern "C" int mf_beside_supported(void) {
     int dev = 0, v = 0;

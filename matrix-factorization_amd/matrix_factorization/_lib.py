@@ -80,6 +80,12 @@ SIGNATURES = {
     "mf_sse_capped": (ctypes.c_int, [
         _P, _P, _P, _I64, _F64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F64,
         _F64, _F64, _P, _I32, _P, _I32, _P, _P]),
+    "mf_sse_slab_workspace_bytes": (ctypes.c_size_t, [_I32]),
+    "mf_sse_slab_plan": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "mf_sse_slab": (ctypes.c_int, [
+        _P, _P, _P, _I64, _F64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F64,
+        _F64, _F64, _P, _I32, _I32, _I32, _I32,       # ..., tab, groups, windows, rows, stride
+        _P, _I32, _P, _P, _P]),                       # ws, max_blocks, out, stream, attrs
     "mf_beside_supported": (ctypes.c_int, []),
     "mf_beside_create": (ctypes.c_int, [_P]),
     "mf_beside_destroy": (None, [_P]),

@@ -204,6 +204,53 @@ def eval_tiles(dtype: str) -> Tuple[int, int]:
     return EVAL_TILES.get(dtype, (1, N_SLICES))
 
 
+# ------------------------------------------------ item-stationary RMSE pass
+# User super-windows per phase of the item-stationary pass (one launch each;
+# MF_SSE_SLAB_W overrides; tools/sse_slab_probe.py).
+SSE_SLAB_WINDOWS = 4
+# The pass is selected by default from this many ratings up, per dtype (None:
+# never).  From the probe's table (profiles/sse_slab/probe.json; DESIGN.md
+# section 5, "Item-stationary RMSE pass"): FP64 at C3 (100M ratings) 4.57 ->
+# 3.33 ms.  Alone on the GPU it also wins on C3's user shards (N = 2 / 4 / 8:
+# 2.32 -> 1.73, 1.27 -> 0.89, 0.61 -> 0.49 ms), but a sharded engine runs its
+# pass capped, beside the next sub-epochs, which was not measured: shapes
+# below 2^26 ratings keep the default pass, and so does C2 (5M ratings: 0.153
+# vs 0.156 ms, a launch per phase and window does not pay).  FP32 at C3: 2.24
+# vs 2.26 ms in the default form (8 waves), so FP32 is not switched (16 waves
+# per workgroup measured 1.81 ms; that form is a probe form only so far).
+SSE_SLAB_MIN_RATINGS = {"float64": 1 << 26, "float32": None}
+
+
+def sse_slab_plan(n_items: int, k: int, dtype: str, n_workgroups: int, lds_budget: int = 0,
+                  pad: int = 0) -> Optional[dict]:
+    """Item groups of the item-stationary pass (mf_sse_slab_plan; no GPU
+    needed): the smallest multiple of ``n_workgroups`` whose largest group's
+    rows and biases fit the LDS budget (0: a CU's), or None where not even
+    one row fits."""
+    out = (ctypes.c_int32 * 5)()
+    if not _lib.load().mf_sse_slab_plan(int(n_items), int(k), DTYPES[dtype][2],
+                                        int(n_workgroups), int(lds_budget), int(pad), out):
+        return None
+    return dict(items=out[0], groups=out[1], phases=out[2], lds=out[3], stride=out[4])
+
+
+def sse_slab_selected(dtype: str, n: int, n_users: int, n_items: int, k: int) -> bool:
+    """Whether an engine of this shape runs the item-stationary pass.
+    MF_SSE_SLAB=1 / 0 forces it on (where it can run) / off.  It cannot run
+    without factors or with user rows of 4 GiB or more; beside mode
+    (MF_SSE_BESIDE=1) keeps the default pass, whose grid its snapshots pin."""
+    env = os.environ.get("MF_SSE_SLAB")
+    size = 4 if dtype == "float32" else 8
+    if env == "0" or k < 1 or n < 1 or n_items < 1 or n_users * k * size >= (1 << 32) - 64:
+        return False
+    if env == "1":
+        return True
+    if os.environ.get("MF_SSE_BESIDE") == "1":
+        return False
+    floor = SSE_SLAB_MIN_RATINGS.get(dtype)
+    return floor is not None and n >= floor
+
+
 # ------------------------------------------------------------ strata plan
 def strata_mix(seed: int, blk: int) -> int:
     """First colour of block ``blk`` (mod its colour count) in the epoch with
@@ -684,6 +731,7 @@ class SGDEngine:
             self._build_eval()
         else:                        # a regrouping's engine: sweeps only, no RMSE pass
             self.eu, self.ei, self.er, self.eval_offs = self.u, self.i, self.r, None
+            self.slab = None
         self.colored = None          # (offsets,) once prepare_colored() ran
         self.strata = None           # StrataPlan once prepare_strata() ran
         self._regroups = []          # relabelled plans: [(engine, user perm, item perm)]
@@ -708,8 +756,12 @@ class SGDEngine:
     def _build_eval(self):
         """Second copy of the ratings in evaluation order (mf_sched_slices):
         the training-RMSE pass walks one item slice per XCD, user by user."""
+        self.slab = None
         if self.bias_only or self.n == 0:
             self.eu, self.ei, self.er, self.eval_offs = self.u, self.i, self.r, None
+            return
+        if sse_slab_selected(self.dtype, self.n, self.n_users, self.n_items, self.k) \
+                and self._build_eval_slab():
             return
         n_chunks, n_slices = eval_tiles(self.dtype)
         if os.environ.get("MF_EVAL_ORDER") == "host":
@@ -724,6 +776,45 @@ class SGDEngine:
         self.er = self.r.index_select(0, d_sched)
         del d_sched
         self.eval_offs = offs
+
+    def _build_eval_slab(self) -> bool:
+        """The item-stationary pass's order instead of the sliced one: ratings
+        by (item group, user), and the device table of each group's first
+        rating at every user super-window boundary (equal user ranges).
+        False where no row fits the LDS budget (the sliced order is built).
+        MF_SSE_SLAB_LDS / MF_SSE_SLAB_PAD / MF_SSE_SLAB_W: probe overrides of
+        the LDS budget in bytes, the row padding in values and the windows."""
+        env = os.environ.get
+        plan = sse_slab_plan(self.n_items, self.k, self.dtype, self._cus(),
+                             int(env("MF_SSE_SLAB_LDS", "0")), int(env("MF_SSE_SLAB_PAD", "0")))
+        if plan is None:
+            return False
+        G, W = plan["groups"], max(1, int(env("MF_SSE_SLAB_W", str(SSE_SLAB_WINDOWS))))
+        with torch.cuda.device(self.dev):
+            nu = self.n_users
+            key = torch.div(self.i.long() * G, self.n_items, rounding_mode="floor") * nu \
+                + self.u.long()
+            skey, order = torch.sort(key, stable=True)
+            del key
+            ub = torch.arange(W + 1, dtype=torch.int64, device=self.dev) * nu // W
+            edges = torch.arange(G, dtype=torch.int64, device=self.dev)[:, None] * nu + ub[None, :]
+            tab = torch.searchsorted(skey, edges.reshape(-1)).reshape(G, W + 1).contiguous()
+            del skey, edges
+            self.eu = self.u.index_select(0, order)
+            self.ei = self.i.index_select(0, order)
+            self.er = self.r.index_select(0, order)
+        self.eval_offs = None
+        self.slab = dict(tab=tab, windows=W, **plan)
+        return True
+
+    def _sse_slab(self, P, Q, bu, bi, ws, out, stream, max_blocks: int = 0, attrs=None) -> None:
+        sl = self.slab
+        with torch.cuda.device(self.dev):
+            _lib.call("mf_sse_slab", _tp(self.eu), _tp(self.ei), _tp(self.er), self.n,
+                      self.global_mean, _tp(bu), _tp(bi), _tp(P), _tp(Q), self.n_users,
+                      self.n_items, self.k, self.kcode, self.dcode, self.gamma, self.min_rating,
+                      self.max_rating, _tp(sl["tab"]), sl["groups"], sl["windows"], sl["items"],
+                      sl["stride"], _tp(ws), int(max_blocks), out, stream, attrs)
 
     def _eval_order_device(self, n_chunks: int, n_slices: int):
         """mf_sched_tiles' order computed on the GPU from the uploaded ids:
@@ -1654,6 +1745,8 @@ class SGDEngine:
         self._bs = False
         if self.bias_only or self.n == 0 or getattr(self, "_regroup_of", None) is not None:
             return None
+        if self.slab is not None:          # (beside mode pins the default pass's grid)
+            return None
         if torch.distributed.is_available() and torch.distributed.is_initialized() \
                 and torch.distributed.get_world_size() > 1:
             return None
@@ -1787,6 +1880,8 @@ class SGDEngine:
                 _lib.call("mf_bias_sse", _tp(self.u), _tp(self.i), _tp(self.r), self.n,
                           self.global_mean, _tp(self.bu), _tp(self.bi), self.dcode,
                           _tp(self.ws), out, self.stream)
+            elif self.slab is not None:
+                self._sse_slab(self.P, self.Q, self.bu, self.bi, self.ws, out, self.stream)
             else:
                 offs = self.eval_offs
                 _lib.call("mf_sse", _tp(self.eu), _tp(self.ei), _tp(self.er), self.n,
@@ -1805,6 +1900,9 @@ class SGDEngine:
         concurrently running pass)."""
         self._ensure_sse_slots(slot + 1)
         out = _VOID(self.sse_buf.data_ptr() + 8 * slot)
+        if self.slab is not None:
+            self._sse_slab(P, Q, bu, bi, ws, out, _VOID(stream.cuda_stream), max_blocks)
+            return
         offs = self.eval_offs
         with torch.cuda.device(self.dev):
             _lib.call("mf_sse_capped", _tp(self.eu), _tp(self.ei), _tp(self.er), self.n,
@@ -1849,13 +1947,17 @@ class SGDEngine:
             ov.setdefault("events", []).append(ev)
         out = _VOID(self.sse_buf.data_ptr() + 8 * slot)
         offs = self.eval_offs
-        with torch.cuda.device(self.dev):
-            _lib.call("mf_sse", _tp(self.eu), _tp(self.ei), _tp(self.er), self.n,
-                      self.global_mean, _tp(ov["bu"]), _tp(ov["bi"]), _tp(ov["P"]),
-                      _tp(ov["Q"]), self.n_users, self.n_items, self.k, self.kcode,
-                      self.dcode, self.gamma, self.min_rating, self.max_rating, _np(offs),
-                      0 if offs is None else len(offs) - 1, _tp(ov["ws"]), out,
-                      _VOID(side.cuda_stream))
+        if self.slab is not None:
+            self._sse_slab(ov["P"], ov["Q"], ov["bu"], ov["bi"], ov["ws"], out,
+                           _VOID(side.cuda_stream))
+        else:
+            with torch.cuda.device(self.dev):
+                _lib.call("mf_sse", _tp(self.eu), _tp(self.ei), _tp(self.er), self.n,
+                          self.global_mean, _tp(ov["bu"]), _tp(ov["bi"]), _tp(ov["P"]),
+                          _tp(ov["Q"]), self.n_users, self.n_items, self.k, self.kcode,
+                          self.dcode, self.gamma, self.min_rating, self.max_rating,
+                          _np(offs), 0 if offs is None else len(offs) - 1, _tp(ov["ws"]),
+                          out, _VOID(side.cuda_stream))
         if timing:
             ov["events"][-1][1].record(side)
         done = torch.cuda.Event()
