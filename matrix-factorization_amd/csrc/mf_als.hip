@@ -30,37 +30,19 @@
 #include <cstring>
 #include <utility>
 
+#include "mf_als_block.hpp"
 #include "mf_common.hpp"
 
 namespace mf {
 
-constexpr int kAlsThreads = 256;
-constexpr int kAlsChunk = 64;        // other-side rows per LDS chunk (32 K-steps)
-constexpr int kAlsMaxFactors = 128;
+// the 4-wave layout's constants and tile enumeration: mf_als_block.hpp
+using alsblk::f32x16;
+using alsblk::kChunk;
+using alsblk::kThreads;
+using alsblk::tile_row;
+using alsblk::Tiles;
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
-
-// MFMA tiles of the symmetric Gramian: column blocks J = 0..NT-1, row blocks
-// I <= J.  Tile q is computed by wave q % 4.  The two right-hand columns
-// (sum t z, sum z) are VALU sums: wave w < NT accumulates column block w.
-template <int NT>
-struct AlsTiles {
-    static constexpr int count = NT * (NT + 1) / 2;
-    static constexpr int per_wave = (count + 3) / 4;
-    static constexpr int I(int q) {
-        for (int J = 0, n = 0; J < NT; ++J)
-            for (int i = 0; i <= J; ++i, ++n)
-                if (n == q) return i;
-        return 0;
-    }
-    static constexpr int J(int q) {
-        for (int J = 0, n = 0; J < NT; ++J)
-            for (int i = 0; i <= J; ++i, ++n)
-                if (n == q) return J;
-        return 0;
-    }
-};
 
 struct AlsArgs {
     const int64_t* ptr;        // n_entities + 1
@@ -86,9 +68,9 @@ __device__ __forceinline__ void als_stamp(const AlsArgs& A, int slot) {
 // right-hand sums of column block WV (lane (r, h): column 32 WV + r, row h).
 template <int NT, int WV>
 __device__ __forceinline__ void als_kstep(const float* zr, float tv, int r,
-                                          f32x16 (&acc)[AlsTiles<NT>::per_wave],
+                                          f32x16 (&acc)[Tiles<NT>::per_wave],
                                           float& fsum, float& ssum) {
-    using TL = AlsTiles<NT>;
+    using TL = Tiles<NT>;
     float zv[NT];
 #pragma unroll
     for (int I = 0; I < NT; ++I) zv[I] = zr[32 * I + r];
@@ -110,9 +92,9 @@ __device__ __forceinline__ void als_kstep(const float* zr, float tv, int r,
 // column block WV -> columns KP, KP + 1.
 template <int NT, int WV>
 __device__ __forceinline__ void als_dump(float* M, int LD, int lane,
-                                         const f32x16 (&acc)[AlsTiles<NT>::per_wave],
+                                         const f32x16 (&acc)[Tiles<NT>::per_wave],
                                          float fsum, float ssum) {
-    using TL = AlsTiles<NT>;
+    using TL = Tiles<NT>;
     constexpr int KP = NT * 32;
     const int col = lane & 31, h = lane >> 5;
 #pragma unroll
@@ -122,7 +104,7 @@ __device__ __forceinline__ void als_dump(float* M, int LD, int lane,
         const int I = TL::I(q), J = TL::J(q);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int row = 32 * I + (i & 3) + 8 * (i >> 2) + 4 * h;
+            const int row = 32 * I + tile_row(i, h);
             M[row * LD + 32 * J + col] = acc[s][i];
             if (I < J) M[(32 * J + col) * LD + row] = acc[s][i];
         }
@@ -138,22 +120,22 @@ __device__ __forceinline__ void als_dump(float* M, int LD, int lane,
     }
 }
 
-// The Gramian of one entity on wave WV's tiles.  Chunks of kAlsChunk other-
+// The Gramian of one entity on wave WV's tiles.  Chunks of kChunk other-
 // side rows are software-pipelined through registers: while the MFMAs
 // consume chunk c from LDS, the rows of chunk c + 1 (ids loaded one chunk
 // earlier) are in flight.  Thread t moves float4 column c4 = t % C4 of rows
-// n = t / C4 + (256 / C4) * w; thread t < kAlsChunk also fetches the rating
+// n = t / C4 + (256 / C4) * w; thread t < kChunk also fetches the rating
 // and the other-side bias of row t (the right-hand side t_n), summing them.
 template <int NT, int WV>
 __device__ __forceinline__ void als_gram_wave(const AlsArgs& A, float* Zc, float* tc, int64_t p0,
                                               int64_t cnt, int lane, float* M, int LD,
                                               float& tsum) {
-    using TL = AlsTiles<NT>;
+    using TL = Tiles<NT>;
     constexpr int KP = NT * 32;
     constexpr int C4 = KP / 4;                    // float4 per row
-    constexpr int RPP = kAlsThreads / C4;         // rows per pass of the block
-    constexpr int NW = kAlsChunk / RPP;           // float4 per thread per chunk
-    static_assert(kAlsThreads % C4 == 0 && kAlsChunk % RPP == 0, "chunk tiling");
+    constexpr int RPP = kThreads / C4;            // rows per pass of the block
+    constexpr int NW = kChunk / RPP;              // float4 per thread per chunk
+    static_assert(kThreads % C4 == 0 && kChunk % RPP == 0, "chunk tiling");
     const int tid = threadIdx.x;
     const int c4 = tid % C4, n0 = tid / C4;
     const int k = A.k;
@@ -174,8 +156,8 @@ __device__ __forceinline__ void als_gram_wave(const AlsArgs& A, float* Zc, float
             ids[w] = n < cnt ? A.other[p0 + n] : -1;
         }
         const int64_t nt = c0 + tid;
-        tid_id = (tid < kAlsChunk && nt < cnt) ? A.other[p0 + nt] : -1;
-        rr = (tid < kAlsChunk && nt < cnt) ? A.r[p0 + nt] : 0.f;
+        tid_id = (tid < kChunk && nt < cnt) ? A.other[p0 + nt] : -1;
+        rr = (tid < kChunk && nt < cnt) ? A.r[p0 + nt] : 0.f;
     };
     auto load_rows = [&](const int (&ids)[NW], float4 (&v)[NW]) __attribute__((always_inline)) {
 #pragma unroll
@@ -201,9 +183,9 @@ __device__ __forceinline__ void als_gram_wave(const AlsArgs& A, float* Zc, float
     load_rows(ids, v);
     float ob = tid_id >= 0 ? A.ob[tid_id] : 0.f;
     float rr_cur = rr;
-    load_ids(kAlsChunk, ids, tid_id, rr);         // chunk 1's ids (may be empty)
-    for (int64_t c0 = 0; c0 < cnt; c0 += kAlsChunk) {
-        const int m = (int)min((int64_t)kAlsChunk, cnt - c0);
+    load_ids(kChunk, ids, tid_id, rr);            // chunk 1's ids (may be empty)
+    for (int64_t c0 = 0; c0 < cnt; c0 += kChunk) {
+        const int m = (int)min((int64_t)kChunk, cnt - c0);
         __syncthreads();                          // previous chunk consumed
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
@@ -211,7 +193,7 @@ __device__ __forceinline__ void als_gram_wave(const AlsArgs& A, float* Zc, float
             *reinterpret_cast<float4*>(Zc + (n0 + RPP * w) * KP + 4 * c4) =
                 ok ? v[w] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        if (tid < kAlsChunk) {
+        if (tid < kChunk) {
             const float t = tid < m ? (rr_cur - A.mu) - ob : 0.f;
             tc[tid] = t;
             tsum += t;
@@ -221,7 +203,7 @@ __device__ __forceinline__ void als_gram_wave(const AlsArgs& A, float* Zc, float
         const float rr_next = rr;
         const int id_next = tid_id;
         load_rows(ids, v);
-        load_ids(c0 + 2 * kAlsChunk, ids, tid_id, rr);
+        load_ids(c0 + 2 * kChunk, ids, tid_id, rr);
         ob = id_next >= 0 ? A.ob[id_next] : 0.f;
         rr_cur = rr_next;
         const int steps = (m + 1) >> 1;
@@ -235,14 +217,14 @@ __device__ __forceinline__ void als_gram_wave(const AlsArgs& A, float* Zc, float
 }
 
 template <int NT>
-__global__ __launch_bounds__(kAlsThreads, 2) void k_als_solve(AlsArgs A) {
+__global__ __launch_bounds__(kThreads, 2) void k_als_solve(AlsArgs A) {
     constexpr int KP = NT * 32;
     constexpr int LD = KP + 3;                    // odd stride: column reads conflict-free
     extern __shared__ __align__(16) float lds[];
-    float* Zc = lds;                              // [kAlsChunk][KP]   (Gramian phase)
-    float* tc = lds + kAlsChunk * KP;             // [kAlsChunk]
+    float* Zc = lds;                              // [kChunk][KP]   (Gramian phase)
+    float* tc = lds + kChunk * KP;                // [kChunk]
     float* M = lds;                               // [KP][LD]          (solve phase)
-    __shared__ float red[kAlsThreads / kWave];
+    __shared__ float red[kThreads / kWave];
 
     const int e = blockIdx.x;
     const int64_t p0 = A.ptr[e], cnt = A.ptr[e + 1] - p0;
@@ -501,7 +483,7 @@ __device__ __forceinline__ void als_lds_dma16(const void* src, void* lds_dst) {
 
 template <int NT>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void k_als_wave(AlsArgs A) {
-    using TL = AlsTiles<NT>;
+    using TL = Tiles<NT>;
     using SH = AlsWaveShape<NT>;
     constexpr int KP = SH::KP, NR = SH::NR, NQ = TL::count;
     constexpr int CR = SH::CR, RPP = SH::RPP, LPR = SH::LPR, PPC = SH::PPC;
@@ -820,12 +802,12 @@ int als_go_wave(const AlsArgs& a, int32_t n, hipStream_t stream) {
 template <int NT>
 int als_go(const AlsArgs& a, int32_t n, hipStream_t stream) {
     constexpr int KP = NT * 32;
-    const size_t lds = std::max((size_t)KP * (KP + 3), (size_t)kAlsChunk * KP + kAlsChunk) *
+    const size_t lds = std::max((size_t)KP * (KP + 3), (size_t)kChunk * KP + kChunk) *
                        sizeof(float);
     auto kfn = k_als_solve<NT>;
     MF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kfn, dim3((unsigned)n), dim3(kAlsThreads), lds, stream, a);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)n), dim3(kThreads), lds, stream, a);
     MF_HIP_CHECK(hipGetLastError());
     return MF_OK;
 }
@@ -836,16 +818,16 @@ void touch_als(hipStream_t s) { hipLaunchKernelGGL(k_touch<7>, dim3(1), dim3(64)
 
 using namespace mf;
 
-extern "C" int32_t mf_als_max_factors(void) { return kAlsMaxFactors; }
+extern "C" int32_t mf_als_max_factors(void) { return alsblk::kMaxFactors; }
 
 static int als_sweep(const int64_t* entity_ptr, const int32_t* other_ids,
                             const void* ratings, int32_t n_entities, double global_mean,
                             const void* other_biases, const void* other_features,
                             void* biases, void* features, int32_t n_factors, int32_t dtype,
                             double reg, void* stream, int64_t* probe) {
-    if (n_entities < 0 || n_factors < 1 || n_factors > kAlsMaxFactors) {
+    if (n_entities < 0 || n_factors < 1 || n_factors > alsblk::kMaxFactors) {
         set_error("mf_als_sweep: n_entities=%d / n_factors=%d (must be in [1, %d])", n_entities,
-                  n_factors, kAlsMaxFactors);
+                  n_factors, alsblk::kMaxFactors);
         return MF_ERR_INVALID;
     }
     if (dtype != MF_F32) {
@@ -867,19 +849,21 @@ static int als_sweep(const int64_t* entity_ptr, const int32_t* other_ids,
     // k_als_wave (default); MF_ALS_KERNEL=block selects the 4-wave
     // k_als_solve (A/B probes)
     const char* ev = std::getenv("MF_ALS_KERNEL");
-    if (ev && std::strcmp(ev, "block") == 0) {
-        if (n_factors <= 32) return als_go<1>(a, n_entities, s);
-        if (n_factors <= 64) return als_go<2>(a, n_entities, s);
-        return als_go<4>(a, n_entities, s);       // 96 columns do not tile 256 lanes
+    const bool block = ev && std::strcmp(ev, "block") == 0;
+    // rows not 16-byte aligned for the DMA (n_factors % 4 != 0): k_als_solve
+    const int nt = alsblk::nt_of(n_factors);
+    if (block || n_factors % 4 != 0) {
+        switch (nt) {
+            case 1: return als_go<1>(a, n_entities, s);
+            case 2: return als_go<2>(a, n_entities, s);
+            default: return als_go<4>(a, n_entities, s);
+        }
     }
-    if (n_factors % 4 != 0) {                     // rows not 16-byte aligned for the DMA
-        if (n_factors <= 32) return als_go<1>(a, n_entities, s);
-        if (n_factors <= 64) return als_go<2>(a, n_entities, s);
-        return als_go<4>(a, n_entities, s);
+    switch (nt) {
+        case 1: return als_go_wave<1>(a, n_entities, s);
+        case 2: return als_go_wave<2>(a, n_entities, s);
+        default: return als_go_wave<4>(a, n_entities, s);
     }
-    if (n_factors <= 32) return als_go_wave<1>(a, n_entities, s);
-    if (n_factors <= 64) return als_go_wave<2>(a, n_entities, s);
-    return als_go_wave<4>(a, n_entities, s);
 }
 
 extern "C" int mf_als_sweep(const int64_t* entity_ptr, const int32_t* other_ids,

@@ -24,102 +24,38 @@
 //      thread branches on the same bits).  No atomics: the same input gives
 //      the same bits.
 //
-// mf_ials.hip is untouched; the shared pieces (tile enumeration, chunk
-// pipeline, dump) are restated here in namespace mf::ials_cg.
+// The tile enumeration and the chunk pipeline of phase 1 are
+// mf_als_block.hpp's, shared with k_ials_solve; the dump differs (it folds reg
+// and the padding diagonal in and writes b to its own vector).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 
+#include "mf_als_block.hpp"
 #include "mf_common.hpp"
 
 namespace mf {
 namespace ials_cg {
 
-constexpr int kThreads = 256;
-constexpr int kChunk = 64;           // rows per LDS chunk (32 K-steps)
-constexpr int kMaxFactors = 128;
+// the 4-wave layout's constants, tile enumeration and chunk pipeline
+using alsblk::aligned16;
+using alsblk::f32x16;
+using alsblk::kChunk;
+using alsblk::kThreads;
+using alsblk::ListArgs;
+using alsblk::nt_of;
+using alsblk::tile_row;
+using alsblk::Tiles;
+
 constexpr int kMaxSteps = 1024;
 constexpr float kRsStop = 1e-30f;    // the recurrence stops once rs is not above this
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-// Upper 32 x 32 tiles of a symmetric (32 NT)^2 matrix: column blocks
-// J = 0..NT-1, row blocks I <= J; tile q belongs to wave q % 4 (the
-// enumeration of mf_als.hip's AlsTiles).
-template <int NT>
-struct Tiles {
-    static constexpr int count = NT * (NT + 1) / 2;
-    static constexpr int per_wave = (count + 3) / 4;
-    static constexpr int I(int q) {
-        for (int J = 0, n = 0; J < NT; ++J)
-            for (int i = 0; i <= J; ++i, ++n)
-                if (n == q) return i;
-        return 0;
-    }
-    static constexpr int J(int q) {
-        for (int J = 0, n = 0; J < NT; ++J)
-            for (int i = 0; i <= J; ++i, ++n)
-                if (n == q) return J;
-        return 0;
-    }
-};
-
-// row of accumulator register i in a 32 x 32 tile (lane half h); the column
-// is lane & 31
-__device__ __forceinline__ int tile_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
-// float4 column c4 of one row (k values, zero past k); vec: rows 16-byte aligned
-__device__ __forceinline__ float4 load_row4(const float* row, int c4, int k, bool vec) {
-    float4 v;
-    const int c = 4 * c4;
-    if (vec) {
-        v = *reinterpret_cast<const float4*>(row + (c < k ? c : 0));
-        if (c >= k) v = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-        v.x = c + 0 < k ? row[c + 0] : 0.f;
-        v.y = c + 1 < k ? row[c + 1] : 0.f;
-        v.z = c + 2 < k ? row[c + 2] : 0.f;
-        v.w = c + 3 < k ? row[c + 3] : 0.f;
-    }
-    return v;
-}
-
-struct CgArgs {
-    const int64_t* ptr;        // n_entities + 1
-    const int32_t* other;      // other-side id per observation (CSR order)
-    const float* r;            // strength per observation (CSR order)
-    const float* oq;           // other-side factor rows (row-major, k)
+struct CgArgs : ListArgs {
     const float* G;            // (k, k): oq^T oq over all rows
     float* feat;               // factor rows (n_entities x k): warm start, result
-    int32_t k;
-    int32_t vec;               // oq rows 16-byte aligned
-    float alpha;
     float reg;
     int32_t steps;
 };
-
-// One K-step (two chunk rows) of wave WV: lane (r, h) holds row 2 s + h.  The
-// A operand of every tile is the row scaled by w; the right-hand side of
-// column block WV adds cf z (cf = (1 + w) [r > 0]).
-template <int NT, int WV>
-__device__ __forceinline__ void cg_kstep(const float* zr, float w, float cf, int r,
-                                         f32x16 (&acc)[Tiles<NT>::per_wave], float& fsum) {
-    using TL = Tiles<NT>;
-    float zv[NT], zw[NT];
-#pragma unroll
-    for (int I = 0; I < NT; ++I) {
-        zv[I] = zr[32 * I + r];
-        zw[I] = zv[I] * w;
-    }
-#pragma unroll
-    for (int s = 0; s < TL::per_wave; ++s) {
-        const int q = WV + 4 * s;
-        if (q < TL::count)
-            acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(zw[TL::I(q)], zv[TL::J(q)], acc[s],
-                                                          0, 0, 0);
-    }
-    if constexpr (WV < NT) fsum = __builtin_fmaf(cf, zv[WV], fsum);
-}
 
 // Accumulator tiles + the matching tile of G (+ reg on the diagonal; padding
 // dimensions k <= a < KP are decoupled: zero row and column, diagonal 1)
@@ -154,82 +90,15 @@ __device__ __forceinline__ void cg_dump(const CgArgs& A, float* M, float* bv, in
     }
 }
 
-// The weighted Gramian of one entity on wave WV's tiles: k_ials_solve's chunk
-// pipeline (chunk c + 1's rows in registers, ids one chunk further ahead).
-// Thread t < kChunk also fetches the strength of chunk row t.
+// The weighted Gramian of one entity on wave WV's tiles (the shared chunk
+// pipeline), then the tiles to M and the right-hand side to bv.
 template <int NT, int WV>
 __device__ __forceinline__ void cg_gram_wave(const CgArgs& A, float* Zc, float* wc, float* cc,
                                              int64_t p0, int64_t cnt, int lane, float* M,
                                              float* bv, int LD) {
-    using TL = Tiles<NT>;
-    constexpr int KP = NT * 32;
-    constexpr int C4 = KP / 4;                    // float4 per row
-    constexpr int RPP = kThreads / C4;            // rows per pass of the block
-    constexpr int NW = kChunk / RPP;              // float4 per thread per chunk
-    static_assert(kThreads % C4 == 0 && kChunk % RPP == 0, "chunk tiling");
-    const int tid = threadIdx.x;
-    const int c4 = tid % C4, n0 = tid / C4;
-    const int k = A.k;
-    const bool vec = A.vec != 0;
-    f32x16 acc[TL::per_wave];
-#pragma unroll
-    for (int s = 0; s < TL::per_wave; ++s)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[s][i] = 0.f;
-    const int r = lane & 31, h = lane >> 5;
-    float fsum = 0.f;
-
-    auto load_ids = [&](int64_t c0, int (&ids)[NW], float& rr) __attribute__((always_inline)) {
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const int64_t n = c0 + n0 + RPP * w;
-            ids[w] = n < cnt ? A.other[p0 + n] : -1;
-        }
-        const int64_t nt = c0 + tid;
-        rr = (tid < kChunk && nt < cnt) ? A.r[p0 + nt] : 0.f;
-    };
-    auto load_rows = [&](const int (&ids)[NW], float4 (&v)[NW]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const int id = ids[w] >= 0 ? ids[w] : 0;
-            v[w] = load_row4(A.oq + (int64_t)id * k, c4, k, vec);
-        }
-    };
-
-    int ids[NW];
-    float rr;
-    float4 v[NW];
-    load_ids(0, ids, rr);
-    load_rows(ids, v);
-    float rr_cur = rr;
-    load_ids(kChunk, ids, rr);                    // chunk 1's ids (may be empty)
-    for (int64_t c0 = 0; c0 < cnt; c0 += kChunk) {
-        const int m = (int)min((int64_t)kChunk, cnt - c0);
-        __syncthreads();                          // previous chunk consumed
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const bool ok = c0 + n0 + RPP * w < cnt;
-            *reinterpret_cast<float4*>(Zc + (n0 + RPP * w) * KP + 4 * c4) =
-                ok ? v[w] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (tid < kChunk) {
-            const float w = tid < m ? A.alpha * rr_cur : 0.f;
-            wc[tid] = w;
-            cc[tid] = (tid < m && rr_cur > 0.f) ? 1.f + w : 0.f;
-        }
-        __syncthreads();
-        // next chunk: rows from the ids already loaded, then the ids after it
-        const float rr_next = rr;
-        load_rows(ids, v);
-        load_ids(c0 + 2 * kChunk, ids, rr);
-        rr_cur = rr_next;
-        const int steps = (m + 1) >> 1;
-        for (int s = 0; s < steps; ++s) {
-            const int n = 2 * s + h;                  // rows past m are zero rows
-            cg_kstep<NT, WV>(Zc + n * KP, wc[n], cc[n], r, acc, fsum);
-        }
-    }
-    __syncthreads();                              // Zc is reused as M below
+    f32x16 acc[Tiles<NT>::per_wave];
+    float fsum;
+    alsblk::weighted_gram_wave<NT, WV>(A, Zc, wc, cc, p0, cnt, lane, acc, fsum);
     cg_dump<NT, WV>(A, M, bv, LD, lane, acc, fsum);
 }
 
@@ -352,9 +221,6 @@ int cg_go(const CgArgs& a, int32_t n, hipStream_t stream) {
     return MF_OK;
 }
 
-inline int nt_of(int k) { return k <= 32 ? 1 : (k <= 64 ? 2 : 4); }   // 96 columns do not tile 256 lanes
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace ials_cg
 
 void touch_ials_cg(hipStream_t s) { hipLaunchKernelGGL(k_touch<9>, dim3(1), dim3(64), 0, s); }
@@ -368,41 +234,10 @@ extern "C" int mf_ials_sweep_cg(const int64_t* entity_ptr, const int32_t* other_
                                 const void* other_features, const void* gram, void* features,
                                 int32_t n_factors, int32_t dtype, double alpha, double reg,
                                 int32_t cg_steps, void* stream) {
-    if (dtype != MF_F32) {
-        set_error("mf_ials_sweep_cg: dtype=%d (float32 only: f32-input MFMA)", dtype);
-        return MF_ERR_INVALID;
-    }
-    if (n_factors < 1 || n_factors > ials_cg::kMaxFactors) {
-        set_error("mf_ials_sweep_cg: n_factors=%d (must be in [1, %d])", n_factors,
-                  ials_cg::kMaxFactors);
-        return MF_ERR_INVALID;
-    }
-    if (!std::isfinite(alpha) || alpha < 0) {
-        set_error("mf_ials_sweep_cg: alpha=%g (must be finite and >= 0)", alpha);
-        return MF_ERR_INVALID;
-    }
-    if (!std::isfinite(reg) || reg <= 0) {
-        set_error("mf_ials_sweep_cg: reg=%g (must be finite and > 0)", reg);
-        return MF_ERR_INVALID;
-    }
-    if (cg_steps < 1 || cg_steps > ials_cg::kMaxSteps) {
-        set_error("mf_ials_sweep_cg: cg_steps=%d (must be in [1, %d])", cg_steps,
-                  ials_cg::kMaxSteps);
-        return MF_ERR_INVALID;
-    }
-    if (n_entities < 0) {
-        set_error("mf_ials_sweep_cg: n_entities=%d (must be >= 0)", n_entities);
-        return MF_ERR_INVALID;
-    }
-    if (n_entities == 0) return MF_OK;
-    const void* need[] = {entity_ptr, other_ids, strengths, other_features, gram, features};
-    const char* names[] = {"entity_ptr", "other_ids", "strengths", "other_features", "gram",
-                           "features"};
-    for (int i = 0; i < 6; ++i)
-        if (!need[i]) {
-            set_error("mf_ials_sweep_cg: %s is NULL", names[i]);
-            return MF_ERR_INVALID;
-        }
+    const int rc = alsblk::check_ials_args("mf_ials_sweep_cg", entity_ptr, other_ids, strengths,
+                                           n_entities, other_features, gram, features, n_factors,
+                                           dtype, alpha, reg, cg_steps, ials_cg::kMaxSteps);
+    if (rc != MF_OK || n_entities == 0) return rc;
     ials_cg::CgArgs a;
     a.ptr = entity_ptr; a.other = other_ids; a.r = static_cast<const float*>(strengths);
     a.oq = static_cast<const float*>(other_features);

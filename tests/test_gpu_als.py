@@ -36,8 +36,7 @@ def _close(a, b, tol):
     return err
 
 
-@pytest.mark.parametrize("k", [8, 20, 32, 64, 100, 128])
-def test_half_sweeps_match_oracle(k):
+def _half_sweeps_match_oracle(k):
     import oracle
     from matrix_factorization.engine import FactorALS, SGDEngine
 
@@ -68,6 +67,24 @@ def test_half_sweeps_match_oracle(k):
     bi_o, Q_o = oracle.als_half_sweep(i, u, r, np.float32(mu), bug, Pg, ni, reg)
     _close(Qg2, Q_o, 2e-4)
     _close(big2, bi_o, 2e-4)
+
+
+@pytest.mark.parametrize("k", [8, 20, 32, 64, 100, 128])
+def test_half_sweeps_match_oracle(k):
+    _half_sweeps_match_oracle(k)
+
+
+# Ranks that are no multiple of 4 go to the 4-wave k_als_solve<1/2/4> (the
+# one-wave kernel's row DMA needs 16-byte rows); MF_ALS_KERNEL=block, read by
+# the library on every call, sends the other ranks there too.
+@pytest.mark.parametrize("k,block", [(1, False), (3, False), (33, False), (65, False),
+                                     (99, False), (8, True), (64, True), (128, True)])
+def test_half_sweeps_match_oracle_block_kernel(k, block, monkeypatch):
+    if block:
+        monkeypatch.setenv("MF_ALS_KERNEL", "block")
+    else:
+        monkeypatch.delenv("MF_ALS_KERNEL", raising=False)
+    _half_sweeps_match_oracle(k)
 
 
 def test_alsmf_fit_matches_oracle():
