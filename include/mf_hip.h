@@ -770,6 +770,89 @@ int mf_cf_predict(const int32_t* entity_ids, const int32_t* other_ids, int64_t n
                   double global_mean, double min_rating, double max_rating,
                   int32_t bound_ratings, double* out, void* stream);
 
+/*
+ * One query against EVERY target: scores, top-k and exact ranks (the
+ * neighbourhood models' recommend_batch / rank_items / evaluate_topk).
+ *   query_side      MF_CF_QUERY_OTHER   the queries are OTHER ids, the targets
+ *                     all n_entities entities (ItemItemCF: a user against
+ *                     every item)
+ *                   MF_CF_QUERY_ENTITY  the queries are ENTITY ids, the targets
+ *                     all n_others others (UserUserCF: a user against every
+ *                     item)
+ *   query_ids       DEVICE, int32, n_query; an id outside its range (-1 =
+ *                   unknown) scores every target at global_mean
+ *   other_ptr .. global_mean               as for mf_cf_predict
+ *   targets_per_block  targets a workgroup walks, 0 = automatic (64);
+ *                   mf_cf_targets_per_block() gives the value used
+ *                   (min(that, n_targets)).  No result depends on it.
+ * The score of query q and target t is, bit for bit, mf_cf_predict's
+ * (bound_ratings = 0) for the corresponding (entity, other) pair: the same
+ * candidates, order at the cut, exact select and FP64 summation order.  A
+ * workgroup takes one query and a block of targets and keeps what its pairs
+ * share on the chip: with MF_CF_QUERY_OTHER the query's list (ids, r > 0,
+ * (double)r - mean[b]) in LDS when it has at most 1024 entries, with
+ * MF_CF_QUERY_ENTITY row S[e, :] in the caches (MF_CF_ROW_LDS=1 in the
+ * environment: in LDS, for up to 4096 entities).  n_query * ceil(n_targets /
+ * targets per block) is at most 2^31 - 1 a call.  No floating-point atomics.
+ *
+ * mf_cf_scores:  out DEVICE, double, n_query x n_targets row-major, written.
+ *
+ * mf_cf_topk:  the scores go as order keys (mf_topk's order: score descending,
+ * NaN last, then target id ascending) into `workspace`, the keys of the pairs
+ * in the exclusion CSR (query q skips targets exclude_items[exclude_ptr[q] ..
+ * exclude_ptr[q+1]); NULL: none; ids out of range are ignored, any order,
+ * duplicates count once) are zeroed, and mf_topk's exact select writes
+ *   out_items       DEVICE, int32, n_query x amount: target ids, -1 padding
+ *   out_scores      DEVICE, double, n_query x amount: scores, NaN padding
+ *   workspace       DEVICE, mf_cf_topk_workspace_bytes(n_query, n_targets) =
+ *                   8 n_query n_targets bytes
+ *   amount          in [1, 2048]
+ *
+ * mf_cf_rank:  the same key matrix and exclusions, then an integer count:
+ *   target_ptr, target_items   DEVICE CSR: query q's targets (any order,
+ *                   repeats allowed)
+ *   out_rank        DEVICE, int32, one per CSR entry: the number of
+ *                   non-excluded candidates that come before the target in
+ *                   mf_cf_topk's order; -1 for a target out of range or
+ *                   excluded
+ *   out_candidates  DEVICE, int32, n_query: the non-excluded candidates
+ *   workspace       DEVICE, mf_cf_rank_workspace_bytes(n_query, n_targets) =
+ *                   8 n_query n_targets bytes
+ * mf_rank's semantics, so utils.ranking_metrics_from_ranks applies unchanged.
+ *
+ * All three: dtype must be MF_F32, query_side one of the two, n_neighbors >= 1,
+ * targets_per_block >= 0, amount in [1, 2048], counts >= 0, no NULL for
+ * query_ids, an output, the workspace or the target CSR (nor, with
+ * n_entities > 0 and n_others > 0, for other_ptr, similarity and mean) -- else
+ * MF_ERR_INVALID, before any device work, with the argument's name in
+ * mf_last_error().  n_query == 0 returns MF_OK.
+ */
+#define MF_CF_QUERY_OTHER 0
+#define MF_CF_QUERY_ENTITY 1
+int32_t mf_cf_targets_per_block(int32_t n_targets, int32_t targets_per_block);
+int mf_cf_scores(const int32_t* query_ids, int32_t n_query, int32_t query_side,
+                 const int64_t* other_ptr, const int32_t* list_entity_ids,
+                 const void* list_ratings, const void* similarity, const double* mean,
+                 int32_t n_entities, int32_t n_others, int32_t dtype, int32_t n_neighbors,
+                 double global_mean, int32_t targets_per_block, double* out, void* stream);
+size_t mf_cf_topk_workspace_bytes(int32_t n_query, int32_t n_targets);
+int mf_cf_topk(const int32_t* query_ids, int32_t n_query, int32_t query_side,
+               const int64_t* other_ptr, const int32_t* list_entity_ids,
+               const void* list_ratings, const void* similarity, const double* mean,
+               int32_t n_entities, int32_t n_others, int32_t dtype, int32_t n_neighbors,
+               double global_mean, int32_t targets_per_block, const int64_t* exclude_ptr,
+               const int32_t* exclude_items, int32_t amount, void* workspace,
+               int32_t* out_items, double* out_scores, void* stream);
+size_t mf_cf_rank_workspace_bytes(int32_t n_query, int32_t n_targets);
+int mf_cf_rank(const int32_t* query_ids, int32_t n_query, int32_t query_side,
+               const int64_t* other_ptr, const int32_t* list_entity_ids,
+               const void* list_ratings, const void* similarity, const double* mean,
+               int32_t n_entities, int32_t n_others, int32_t dtype, int32_t n_neighbors,
+               double global_mean, int32_t targets_per_block, const int64_t* exclude_ptr,
+               const int32_t* exclude_items, const int64_t* target_ptr,
+               const int32_t* target_items, void* workspace, int32_t* out_rank,
+               int32_t* out_candidates, void* stream);
+
 /* ---------------- BPR: Bayesian personalised ranking ---------------------- */
 
 /*

@@ -15,9 +15,7 @@
 //   k_cf_predict     LDS = 8 KiB of keys + 1 KiB of bins (17 per CU by LDS,
 //                    so the 16-workgroup-per-CU cap is what binds)
 // No floating-point atomics anywhere: equal inputs give equal bits.
-#include <cmath>
-
-#include "mf_common.hpp"
+#include "mf_cf.hpp"
 
 namespace mf {
 namespace cf {
@@ -25,8 +23,6 @@ namespace cf {
 constexpr int kAutoPassCols = 2048;          // 16 KiB of FP64 accumulators
 constexpr int kMaxPassCols = 4096;           // 32 KiB: 5 workgroups per CU still
 constexpr int kSearchMin = 128;              // lists longer than this are range-searched per pass
-constexpr int kKeysLds = 1024;               // longest list whose keys stay in LDS
-constexpr int64_t kMaxGrid = 1 << 25;        // workgroups of one wave: 2^31 threads a launch
 
 // ------------------------------------------------------------- statistics
 // One thread per entity, its list read in list order: sum and sum of squares
@@ -144,21 +140,6 @@ k_cf_similarity(const SimArgs A) {
 }
 
 // ------------------------------------------------------------- prediction
-// Total order at the cut: similarity descending, then entity id ascending.
-// key = (monotone image of the float's bits) << 32 | ~id is larger for what
-// comes first, distinct per candidate and never 0 (ids are < 2^31).
-__device__ __forceinline__ uint64_t make_key(float s, int32_t id) {
-    if (s == 0.f) s = 0.f;                            // -0 and +0 tie
-    const uint32_t b = __float_as_uint(s);
-    const uint32_t m = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ((uint64_t)m << 32) | (uint32_t)~(uint32_t)id;
-}
-__device__ __forceinline__ float key_sim(uint64_t k) {
-    const uint32_t m = (uint32_t)(k >> 32);
-    return __uint_as_float((m & 0x80000000u) ? (m & 0x7fffffffu) : ~m);
-}
-__device__ __forceinline__ int32_t key_id(uint64_t k) { return (int32_t)~(uint32_t)k; }
-
 struct PredArgs {
     const int32_t* ent; const int32_t* oth; int64_t n_pairs;
     const int64_t* optr; const int32_t* oent; const float* orr;
@@ -168,12 +149,8 @@ struct PredArgs {
     double global_mean, lo, hi;
 };
 
-// One wave per pair (e, o).  The candidates are o's entries with r > 0 and
-// id != e; their keys stay in LDS for lists of up to kKeysLds entries and are
-// rebuilt from S on every read for longer ones.  With more candidates than
-// n_neighbors the n_neighbors-th largest key is found by an 8-pass radix
-// select (256 integer bins per pass, most significant byte first): exact for
-// any list length, linear in it.
+// One wave per pair (e, o): pair_predict (mf_cf.hpp) over o's list.  The
+// candidates are o's entries with r > 0 and id != e.
 __global__ void __launch_bounds__(kWave)
 k_cf_predict(const PredArgs A) {
     __shared__ uint64_t keys[kKeysLds];
@@ -186,86 +163,21 @@ k_cf_predict(const PredArgs A) {
         pred = A.global_mean;                         // unknown id (-1)
     } else {
         const int64_t beg = A.optr[o], end = A.optr[o + 1];
-        const int64_t len = end - beg;
-        const bool in_lds = len <= kKeysLds;
         const float* srow = A.S + (size_t)e * (size_t)A.n_entities;
-        auto build = [&](int64_t t) -> uint64_t {     // 0: not a candidate
-            const int32_t b = A.oent[t];
-            if ((uint32_t)b >= (uint32_t)A.n_entities || b == e || !(A.orr[t] > 0.f)) return 0;
+        auto build = [&](int64_t j) -> uint64_t {     // 0: not a candidate
+            const int32_t b = A.oent[beg + j];
+            if ((uint32_t)b >= (uint32_t)A.n_entities || b == e || !(A.orr[beg + j] > 0.f))
+                return 0;
             return make_key(srow[b], b);
         };
-        uint32_t cnt = 0;
-        for (int64_t t = beg + lane; t < end; t += kWave) {
-            const uint64_t k = build(t);
-            if (in_lds) keys[t - beg] = k;
-            cnt += k != 0;
-        }
-        cnt = wave_sum(cnt);
-        __syncthreads();
-        auto key_at = [&](int64_t t) -> uint64_t { return in_lds ? keys[t - beg] : build(t); };
-
-        uint64_t cut = 1;                             // keep every candidate (keys are >= 2^31)
-        if (cnt > (uint32_t)A.n_neighbors) {
-            uint64_t prefix = 0;                      // the cut's bytes above the current one
-            uint32_t want = (uint32_t)A.n_neighbors;  // rank of the cut among keys matching prefix
-            for (int sh = 56; sh >= 0; sh -= 8) {
-                for (int c = lane; c < 256; c += kWave) bins[c] = 0;
-                __syncthreads();
-                for (int64_t t = beg + lane; t < end; t += kWave) {
-                    const uint64_t k = key_at(t);
-                    if (k != 0 && (sh == 56 || (k >> (sh + 8)) == prefix))
-                        atomicAdd(&bins[(uint32_t)(k >> sh) & 255u], 1u);
-                }
-                __syncthreads();
-                // lane l owns bins 4l .. 4l+3; suf = count in this lane's bins and above
-                const uint32_t h0 = bins[4 * lane], h1 = bins[4 * lane + 1],
-                               h2 = bins[4 * lane + 2], h3 = bins[4 * lane + 3];
-                const uint32_t own = h0 + h1 + h2 + h3;
-                uint32_t suf = own;
-#pragma unroll
-                for (int d = 1; d < kWave; d <<= 1) {
-                    const uint32_t v = __shfl_down(suf, d, kWave);
-                    if (lane + d < kWave) suf += v;
-                }
-                const unsigned long long has = __ballot(suf >= want);
-                const int src = 63 - __builtin_clzll(has);        // has != 0: cnt > want
-                uint32_t above = suf - own, digit;                // counted above this lane
-                if (above + h3 >= want) digit = 3;
-                else if ((above += h3) + h2 >= want) digit = 2;
-                else if ((above += h2) + h1 >= want) digit = 1;
-                else { above += h1; digit = 0; }
-                digit = (uint32_t)bcast_i32((int)(4 * lane + digit), src);
-                want -= (uint32_t)bcast_i32((int)above, src);
-                prefix = (prefix << 8) | digit;
-                __syncthreads();
-            }
-            cut = prefix;
-        }
-        double num = 0.0, den = 0.0;
-        for (int64_t t = beg + lane; t < end; t += kWave) {
-            const uint64_t k = key_at(t);
-            if (k >= cut) {                           // k == 0 never is
-                const double s = (double)key_sim(k);
-                num = num + s * ((double)A.orr[t] - A.mean[key_id(k)]);
-                den = den + fabs(s);
-            }
-        }
-        num = wave_sum(num);
-        den = wave_sum(den);
-        const double me = A.mean[e];
-        pred = den > 0.0 ? me + num / den : me;
+        auto dev = [&](int64_t j, uint64_t k) -> double {
+            return (double)A.orr[beg + j] - A.mean[key_id(k)];
+        };
+        pred = pair_predict(keys, bins, end - beg, A.n_neighbors, lane, A.mean[e], build, dev,
+                            [] { __syncthreads(); });
     }
     if (A.bound) pred = fmax(A.lo, fmin(A.hi, pred));
     if (lane == 0) A.out[p] = pred;
-}
-
-inline bool null_arg(const char* fn, const void* const* need, const char* const* names, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!need[i]) {
-            set_error("%s: %s is NULL", fn, names[i]);
-            return true;
-        }
-    return false;
 }
 
 }  // namespace cf

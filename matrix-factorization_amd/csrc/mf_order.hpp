@@ -60,4 +60,16 @@ __device__ __forceinline__ bool excluded(const int64_t* ptr, const int32_t* item
     return false;
 }
 
+// mf_topk.hip's stage 2 for any [nq x n_items] matrix of order keys (0 = no
+// candidate), also used by mf_cf_topk.hip: topk_exclude_keys zeroes the keys
+// of the CSR pairs (k_topk_exclude); topk_select_f64 does that (ex_ptr or
+// ex_items null: not) and writes each row's best `amount` (<= 2048) by (key
+// desc, id asc), padded with id -1 / NaN (k_topk_select<double>).  Both only
+// enqueue.
+void topk_exclude_keys(uint64_t* keys, int32_t nq, int32_t n_items, const int64_t* ex_ptr,
+                       const int32_t* ex_items, hipStream_t stream);
+void topk_select_f64(uint64_t* keys, int32_t nq, int32_t n_items, const int64_t* ex_ptr,
+                     const int32_t* ex_items, int32_t amount, int32_t* out_items,
+                     double* out_scores, hipStream_t stream);
+
 }  // namespace mf

@@ -1913,6 +1913,25 @@ inline int topk_mw_splits(int32_t nq, int32_t n_items) {
     return (int)std::max<int64_t>(1, s);
 }
 
+void topk_exclude_keys(uint64_t* keys, int32_t nq, int32_t n_items, const int64_t* ex_ptr,
+                       const int32_t* ex_items, hipStream_t stream) {
+    hipLaunchKernelGGL(k_topk_exclude, dim3((unsigned)nq), dim3(kBlock), 0, stream, keys, n_items,
+                       ex_ptr, ex_items);
+}
+
+// Stage 2 of the two-stage path on an [nq x n_items] key matrix: the excluded
+// pairs' keys are zeroed, then each row's best `amount` are selected and sorted
+template <typename T>
+inline void topk_from_keys(uint64_t* keys, int32_t nq, int32_t n_items, const int64_t* ex_ptr,
+                           const int32_t* ex_items, int32_t amount, int32_t* out_items,
+                           T* out_scores, hipStream_t stream) {
+    if (ex_ptr && ex_items) topk_exclude_keys(keys, nq, n_items, ex_ptr, ex_items, stream);
+    int a2 = 1;
+    while (a2 < amount) a2 <<= 1;
+    hipLaunchKernelGGL(k_topk_select<T>, dim3((unsigned)nq), dim3(kBlock), 0, stream,
+                       (const uint64_t*)keys, n_items, amount, a2, out_items, out_scores);
+}
+
 struct TopkLaunch {
     const int32_t* users; int32_t nq; double mu; const void* bu; const void* bi;
     const void* P; const void* Q; int32_t n_items; int32_t k; double gamma, lo, hi;
@@ -1953,17 +1972,19 @@ struct TopkLaunch {
         const unsigned bx = (unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
         hipLaunchKernelGGL((k_topk_scores<T, GS, V, KERN>), dim3(bx, (unsigned)nq),
                            dim3(kBlock), 0, stream, a);
-        if (ex_ptr && ex_items)
-            hipLaunchKernelGGL(k_topk_exclude, dim3((unsigned)nq), dim3(kBlock), 0, stream,
-                               a.keys, n_items, ex_ptr, ex_items);
-        int a2 = 1;
-        while (a2 < amount) a2 <<= 1;
-        hipLaunchKernelGGL(k_topk_select<T>, dim3((unsigned)nq), dim3(kBlock), 0, stream,
-                           (const uint64_t*)ws, n_items, amount, a2, out_items, (T*)out_scores);
+        topk_from_keys<T>(a.keys, nq, n_items, ex_ptr, ex_items, amount, out_items,
+                          (T*)out_scores, stream);
         MF_HIP_CHECK(hipGetLastError());
         return MF_OK;
     }
 };
+
+void topk_select_f64(uint64_t* keys, int32_t nq, int32_t n_items, const int64_t* ex_ptr,
+                     const int32_t* ex_items, int32_t amount, int32_t* out_items,
+                     double* out_scores, hipStream_t stream) {
+    topk_from_keys<double>(keys, nq, n_items, ex_ptr, ex_items, amount, out_items, out_scores,
+                           stream);
+}
 
 void touch_topk(hipStream_t s) { hipLaunchKernelGGL(k_touch<6>, dim3(1), dim3(64), 0, s); }
 

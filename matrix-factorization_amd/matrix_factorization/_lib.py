@@ -32,6 +32,7 @@ MF_FLAG_CLASSES_SHIFT = 24       # bits 24..27: user-range classes - 1
 MF_STRATA_MAX_CLASSES = 4
 MF_ERR_CAPACITY = 3
 MF_DELTA_TAKE, MF_DELTA_APPLY = 0, 1
+MF_CF_QUERY_OTHER, MF_CF_QUERY_ENTITY = 0, 1
 KERNEL_CODES = {"linear": MF_LINEAR, "sigmoid": MF_SIGMOID, "rbf": MF_RBF}
 
 _P = ctypes.c_void_p
@@ -143,6 +144,18 @@ SIGNATURES = {
     "mf_cf_predict": (ctypes.c_int, [
         _P, _P, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32,   # ..., n_ent n_oth dtype nn
         _F64, _F64, _F64, _I32, _P, _P]),                           # mu min max bound out stream
+    "mf_cf_targets_per_block": (_I32, [_I32, _I32]),
+    "mf_cf_scores": (ctypes.c_int, [
+        _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32,  # query side, lists, S, mean, ...
+        _F64, _I32, _P, _P]),                                       # mu targets/block out stream
+    "mf_cf_topk_workspace_bytes": (ctypes.c_size_t, [_I32, _I32]),
+    "mf_cf_topk": (ctypes.c_int, [
+        _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F64, _I32,
+        _P, _P, _I32, _P, _P, _P, _P]),               # exclusions, amount, ws, items, scores, stream
+    "mf_cf_rank_workspace_bytes": (ctypes.c_size_t, [_I32, _I32]),
+    "mf_cf_rank": (ctypes.c_int, [
+        _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F64, _I32,
+        _P, _P, _P, _P, _P, _P, _P, _P]),             # exclusions, targets, ws, rank, cand, stream
     "mf_bpr_max_factors": (ctypes.c_int32, []),
     "mf_bpr_sample": (ctypes.c_int, [
         _P, _P, _P, _I64, _P, _P, _I32, _I32,         # order, positives, n, CSR, n_users n_items

@@ -21,7 +21,11 @@ entity e and other o takes the entities b != e that o rated above 0, keeps the
 (m_e with no neighbour or a zero denominator, the global mean for an unknown
 id).  Statistics, similarity and prediction run on the GPU (mf_cf_stats,
 mf_cf_similarity, mf_cf_predict); the similarity is a float32 matrix in HBM,
-means and predictions are FP64.
+means and predictions are FP64.  ``recommend_batch``, ``rank_items`` and
+``evaluate_topk`` (ranking.RankingMixin, as for the factor models) score every
+item for a user in one pass that keeps what the user's pairs share on the chip
+(mf_cf_topk, mf_cf_rank): the same predictions bit for bit, ordered by score
+descending and internal item id ascending.
 
 Three deliberate departures from the reference:
 
@@ -44,7 +48,9 @@ from __future__ import annotations
 import numpy as np
 import pandas as pd
 
+from . import _lib
 from .neighbours import DEFAULT_MAX_SIMILARITY_BYTES, NeighbourEngine, check_similarity_bytes
+from .ranking import RankingMixin
 from .recommender_base import RecommenderBase
 
 METRICS = ("cosine", "pearson")
@@ -66,7 +72,24 @@ def _warn_if_no_device(name: str) -> None:
                       RuntimeWarning, stacklevel=3)
 
 
-class _NeighbourhoodCF(RecommenderBase):
+class _UserQueries:
+    """ranking.RankingMixin's backend over a NeighbourEngine: the queries are
+    users and the targets all items, whichever of the two the entities are."""
+
+    def __init__(self, engine: NeighbourEngine, side: int, n_neighbors: int, global_mean: float):
+        self.engine, self.side = engine, side
+        self.n_neighbors, self.global_mean = n_neighbors, global_mean
+
+    def topk(self, uid, amount, ex_ptr=None, ex_items=None):
+        return self.engine.topk(uid, self.side, self.n_neighbors, self.global_mean, amount,
+                                ex_ptr, ex_items)
+
+    def rank(self, uid, tgt_ptr, tgt_items, ex_ptr=None, ex_items=None):
+        return self.engine.rank(uid, self.side, self.n_neighbors, self.global_mean, tgt_ptr,
+                                tgt_items, ex_ptr, ex_items)
+
+
+class _NeighbourhoodCF(RankingMixin, RecommenderBase):
     """Shared body of ItemItemCF / UserUserCF; ``_ENTITY`` names the side the
     similarity is taken over."""
 
@@ -116,6 +139,14 @@ class _NeighbourhoodCF(RecommenderBase):
             state.setdefault(key, default)
         self.__dict__.update(state)
         _warn_if_no_device(type(self).__name__)
+
+    def _ranking_backend(self) -> _UserQueries:
+        """recommend_batch / rank_items / evaluate_topk (ranking.RankingMixin):
+        a user is an OTHER of the item-item model and an ENTITY of the
+        user-user one; the engine is rebuilt after unpickling, as for predict."""
+        side = _lib.MF_CF_QUERY_OTHER if self._ENTITY == "item" else _lib.MF_CF_QUERY_ENTITY
+        return _UserQueries(self._fitted_engine(), side, int(self.n_neighbors),
+                            float(self.global_mean))
 
     # -------------------------------------------------------------- API
     def fit(self, X: pd.DataFrame, y: pd.Series):

@@ -7,6 +7,9 @@ ascending in the other's id, other-major with each list ascending in the
 entity's id: the order mf_cf_similarity's bitwise symmetry rests on), the
 statistics and the similarity are computed once (mf_cf_stats,
 mf_cf_similarity), and predict() scores pairs in chunks (mf_cf_predict).
+scores() / topk() / rank() take every target for a batch of queries in one
+pass (mf_cf_scores, mf_cf_topk, mf_cf_rank): the same predictions bit for bit,
+the queries in chunks that keep the key workspace within ``topk_ws_budget``.
 Ratings are float32 on the device; means, norms and predictions are FP64.
 """
 
@@ -109,3 +112,127 @@ class NeighbourEngine:
                           float(max_rating), int(bool(bound)), _VOID(out.data_ptr() + 8 * c0),
                           self.stream)
         return out.cpu().numpy()
+
+    # ------------------------------------------- one query against every target
+    # key workspace of one mf_cf_topk / mf_cf_rank launch (8 B per query and
+    # target); queries beyond this budget go in further launches
+    topk_ws_budget = 1 << 30
+    # targets a workgroup of k_cf_scores walks (0: the library's choice)
+    targets_per_block = 0
+
+    def n_targets(self, side: int) -> int:
+        return self.n_entities if side == _lib.MF_CF_QUERY_OTHER else self.n_others
+
+    def _query_chunk(self, side: int) -> int:
+        """Queries per launch: the key workspace within ``topk_ws_budget`` and
+        the grid (one workgroup per query and block of targets) within 2^31 - 1."""
+        nt = self.n_targets(side)
+        if nt == 0:
+            return 1 << 20
+        tpb = _lib.load().mf_cf_targets_per_block(nt, int(self.targets_per_block))
+        blocks = (nt + tpb - 1) // tpb
+        return max(1, min(int(self.topk_ws_budget) // (8 * nt), (2**31 - 1) // blocks))
+
+    def _model_args(self, n_neighbors: int, global_mean: float) -> tuple:
+        optr, oent, orr = self.other_csr
+        return (_tp(optr), _tp(oent), _tp(orr), _tp(self.S), _tp(self.mean), self.n_entities,
+                self.n_others, _lib.MF_F32, int(n_neighbors), float(global_mean),
+                int(self.targets_per_block))
+
+    def _to(self, a, dtype) -> torch.Tensor:
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self.dev)
+
+    def _exclusions(self, nq: int, ex_ptr, ex_items):
+        """The exclusion CSR on the device (offsets from 0), or (None, None)."""
+        if ex_ptr is None:
+            return None, None
+        ex_ptr = np.ascontiguousarray(ex_ptr, np.int64)
+        if len(ex_ptr) != nq + 1:
+            raise ValueError("ex_ptr needs n_query + 1 offsets")
+        ex_items = np.ascontiguousarray(ex_items, np.int32)[ex_ptr[0]:ex_ptr[-1]]
+        return (self._to(ex_ptr - ex_ptr[0], np.int64),
+                self._to(ex_items if len(ex_items) else np.zeros(1, np.int32), np.int32))
+
+    def scores(self, queries: np.ndarray, side: int, n_neighbors: int,
+               global_mean: float) -> np.ndarray:
+        """FP64 scores [n_query, n_targets] of every target for each query id
+        (mf_cf_scores): ``predict(bound=False)`` of the corresponding pairs, bit
+        for bit.  side: _lib.MF_CF_QUERY_OTHER (queries are other ids, targets
+        the entities) or MF_CF_QUERY_ENTITY (queries are entity ids, targets
+        the others); -1 = unknown id."""
+        nq, nt = len(queries), self.n_targets(side)
+        out = torch.empty((nq, nt), dtype=torch.float64, device=self.dev)
+        if nq and nt:
+            chunk = self._query_chunk(side)
+            with torch.cuda.device(self.dev):
+                d_q = self._to(queries, np.int32)
+                for q0 in range(0, nq, chunk):
+                    m = min(chunk, nq - q0)
+                    _lib.call("mf_cf_scores", _VOID(d_q.data_ptr() + 4 * q0), m, int(side),
+                              *self._model_args(n_neighbors, global_mean),
+                              _VOID(out.data_ptr() + 8 * nt * q0), self.stream)
+        return out.cpu().numpy()
+
+    def topk(self, queries: np.ndarray, side: int, n_neighbors: int, global_mean: float,
+             amount: int, ex_ptr=None, ex_items=None):
+        """Best ``amount`` targets per query (mf_cf_topk): (target ids int32
+        [n_query, amount], scores float64), score descending then id ascending,
+        padded with -1 / NaN.  ``ex_ptr`` / ``ex_items``: optional CSR
+        exclusions (query q skips targets ex_items[ex_ptr[q]:ex_ptr[q+1]])."""
+        nq, nt, amount = len(queries), self.n_targets(side), int(amount)
+        if nq == 0 or amount == 0:
+            return (np.full((nq, amount), -1, np.int32),
+                    np.full((nq, amount), np.nan, np.float64))
+        items = torch.empty((nq, amount), dtype=torch.int32, device=self.dev)
+        scores = torch.empty((nq, amount), dtype=torch.float64, device=self.dev)
+        chunk = min(nq, self._query_chunk(side))
+        with torch.cuda.device(self.dev):
+            d_q = self._to(queries, np.int32)
+            d_ptr, d_ex = self._exclusions(nq, ex_ptr, ex_items)
+            ws = torch.empty(max(8 * chunk * nt, 8), dtype=torch.uint8, device=self.dev)
+            for q0 in range(0, nq, chunk):
+                m = min(chunk, nq - q0)
+                # CSR offsets stay absolute: the chunk's ptr array starts at row q0
+                dp = None if d_ptr is None else _VOID(d_ptr.data_ptr() + 8 * q0)
+                _lib.call("mf_cf_topk", _VOID(d_q.data_ptr() + 4 * q0), m, int(side),
+                          *self._model_args(n_neighbors, global_mean), dp, _tp(d_ex), amount,
+                          _tp(ws), _VOID(items.data_ptr() + 4 * amount * q0),
+                          _VOID(scores.data_ptr() + 8 * amount * q0), self.stream)
+        return items.cpu().numpy(), scores.cpu().numpy()
+
+    def rank(self, queries: np.ndarray, side: int, n_neighbors: int, global_mean: float,
+             tgt_ptr: np.ndarray, tgt_items: np.ndarray, ex_ptr=None, ex_items=None):
+        """Exact rank of each target among its query's candidates (mf_cf_rank):
+        (ranks int32[n_targets], n_candidates int32[n_query]), SGDEngine.rank's
+        contract: ``tgt_ptr`` / ``tgt_items`` are a CSR of target ids per query
+        (any order, repeats allowed); a target out of range or excluded for
+        its query gets rank -1."""
+        nq, nt = len(queries), self.n_targets(side)
+        tgt_ptr = np.ascontiguousarray(tgt_ptr, np.int64)
+        tgt_items = np.ascontiguousarray(tgt_items, np.int32)
+        if len(tgt_ptr) != nq + 1:
+            raise ValueError("tgt_ptr needs n_query + 1 offsets")
+        if nq == 0:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32)
+        tgt_ptr = tgt_ptr - tgt_ptr[0]
+        n_tgt = int(tgt_ptr[-1])
+        if np.any(np.diff(tgt_ptr) < 0) or n_tgt > len(tgt_items):
+            raise ValueError("tgt_ptr must be non-decreasing and end within tgt_items")
+        ranks = torch.empty(max(n_tgt, 1), dtype=torch.int32, device=self.dev)
+        cands = torch.empty(nq, dtype=torch.int32, device=self.dev)
+        chunk = min(nq, self._query_chunk(side))
+        with torch.cuda.device(self.dev):
+            d_q = self._to(queries, np.int32)
+            d_ptr, d_ex = self._exclusions(nq, ex_ptr, ex_items)
+            d_tp = self._to(tgt_ptr, np.int64)
+            d_ti = self._to(tgt_items[:n_tgt] if n_tgt else np.zeros(1, np.int32), np.int32)
+            ws = torch.empty(max(8 * chunk * nt, 8), dtype=torch.uint8, device=self.dev)
+            for q0 in range(0, nq, chunk):
+                m = min(chunk, nq - q0)
+                # both CSRs keep absolute offsets: their ptr arrays start at row q0
+                dp = None if d_ptr is None else _VOID(d_ptr.data_ptr() + 8 * q0)
+                _lib.call("mf_cf_rank", _VOID(d_q.data_ptr() + 4 * q0), m, int(side),
+                          *self._model_args(n_neighbors, global_mean), dp, _tp(d_ex),
+                          _VOID(d_tp.data_ptr() + 8 * q0), _tp(d_ti), _tp(ws), _tp(ranks),
+                          _VOID(cands.data_ptr() + 4 * q0), self.stream)
+        return ranks[:n_tgt].cpu().numpy(), cands.cpu().numpy()
