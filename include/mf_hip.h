@@ -300,8 +300,9 @@ int32_t mf_strata_slots_waves(int32_t n_factors, int32_t dtype, int32_t waves);
  * slice_offsets (HOST, nullable, n_slices + 1 <= 129 entries): the ratings
  * are ordered by mf_sched_slices; slice x is walked by the workgroups
  * b % n_slices == x (XCD-local Q slices).  NULL = one slice.  n_slices > 8
- * and a multiple of 8 (mf_sched_tiles): the tiles are walked in phases of 8,
- * by a resident grid for FP64 (MF_SSE_PHASED=0: dispatch-ordered phases).
+ * and a multiple of 8 (mf_sched_tiles): the grid is cut into n_slices / 8
+ * consecutive parts in dispatch order and part p walks slices 8 p .. 8 p + 7,
+ * one per XCD.  (Placement only changes speed; 8 slices measured fastest.)
  * n_users / n_items: rows of user_features / item_features (every id must
  * be below them).
  */
@@ -1056,10 +1057,11 @@ int mf_sched_slices(const int32_t* user_ids, const int32_t* item_ids,
  * serves: the pass is read-only).  Users are cut into n_chunks contiguous id
  * ranges of about equal rating counts, items into n_slices id ranges; tile
  * c * n_slices + s holds the ratings of user chunk c and item slice s, users
- * ascending inside a tile.  With n_slices a multiple of 8 and the offsets
- * passed to mf_sse, the FP64 pass walks the tiles in phases of 8 (one per
- * XCD) with a resident grid (k_sse_phased), so each XCD's L2 holds one
- * 1/n_slices item slice at a time.
+ * ascending inside a tile; (1, n_slices) is mf_sched_slices' order.  With
+ * the offsets passed to mf_sse and more than 8 tiles (a multiple of 8), the
+ * pass deals the tiles 8 at a time (one per XCD) in dispatch order.  The
+ * library's own pass uses mf_sched_slices' 8 slices: every finer tiling
+ * measured slower.
  *   n_chunks * n_slices <= 128
  *   sched_out      host, n: rating indices in that order
  *   tile_offsets   host, n_chunks * n_slices + 1

@@ -1,8 +1,9 @@
 // mf_rows.hpp -- the two hot kernels of the KernelMF path and their launchers:
 //   k_sgd_batch  one conflict-free batch of SGD updates (kernels.py:108-327
 //                applied to every rating of the batch)
-//   k_sse_stream training sum of squared errors (_calculate_rmse,
-//                kernel_matrix_factorization.py:240-317)
+//   k_sse_lean   training sum of squared errors (_calculate_rmse,
+//                kernel_matrix_factorization.py:240-317); k_sse_stream where
+//                P or Q is >= 4 GiB, k_sse_slab as the item-stationary form
 //
 // Row layout.  A factor row of k values is moved by a
 // GROUP of GS lanes; each lane moves W consecutive values per access (W = 4
@@ -39,12 +40,7 @@ __device__ __forceinline__ void st(X* p, X v) {
     else *p = v;
 }
 
-// User-row access policy POL of k_sgd_batch: 0 plain, 1 non-temporal
-// global ops, >= 2 buffer ops with explicit gfx950 cache-policy bits
-// (aux: sc0 = 1, nt = 2, sc1 = 16) -- table kPolAux, for the L2-residency
-// experiments of tools/sweep_sgd.py.
-struct PolAux { int ld, st; };
-constexpr PolAux kPolAux[8] = {{0, 0}, {0, 0}, {0, 0}, {2, 16}, {16, 16}, {17, 17}, {19, 19}, {2, 2}};
+// Buffer ops of the read passes (AUX: gfx950 cache-policy bits).
 constexpr int kBufDword3 = 0x00020000;     // raw buffer, gfx9 family
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, uint64_t bytes) {
@@ -98,7 +94,6 @@ struct SgdArgs {
     int32_t upd_item;
     int32_t swizzle;
     int32_t* claim;         // nullable: 8 per-slice tile counters of this launch
-    uint64_t p_bytes;       // bytes of P (buffer-policy range; < 4 GiB when POL >= 2)
     Hyper<T> h;
 };
 
@@ -117,7 +112,7 @@ struct ReadArgs {
     T* out;
     double* partials;
     Hyper<T> h;
-    // byte sizes of P, Q, Bu, Bi (buffer-load ranges of k_sse_owned; < 4 GiB)
+    // byte sizes of P, Q, Bu, Bi (buffer-load ranges of the passes; < 4 GiB)
     uint64_t p_bytes, q_bytes, bu_bytes, bi_bytes;
 };
 
@@ -199,14 +194,11 @@ struct SlotsFor {
 
 // Gather the rows of S rating slots: all loads issued before any use;
 // indices clamped so no load sits behind a branch; vector slots past the
-// row end are zeroed afterwards.
+// row end are zeroed afterwards.  POL: 0 plain, 1 non-temporal loads.
 template <typename T, int W, int GS, int V, int S, int POL>
 __device__ __forceinline__ void gather_rows(const T* base, const int (&id)[S], int k, int kv, int l,
-                                            typename VecOf<T, W>::type (&out)[S][V],
-                                            uint64_t bytes = 0) {
+                                            typename VecOf<T, W>::type (&out)[S][V]) {
     using VT = typename VecOf<T, W>::type;
-    [[maybe_unused]] __amdgpu_buffer_rsrc_t rs;
-    if constexpr (POL >= 2) rs = buf_rsrc(base, bytes);
 #pragma unroll
     for (int x = 0; x < S; ++x) {
         const VT* row = reinterpret_cast<const VT*>(base + (int64_t)id[x] * k);
@@ -214,11 +206,7 @@ __device__ __forceinline__ void gather_rows(const T* base, const int (&id)[S], i
         for (int v = 0; v < V; ++v) {
             const int vi = v * GS + l;
             const int vc = vi < kv ? vi : kv - 1;
-            if constexpr (POL >= 2)
-                out[x][v] = buf_ld<kPolAux[POL].ld, VT>(
-                    rs, (uint32_t)(((uint32_t)id[x] * (uint32_t)k + (uint32_t)(vc * W)) * sizeof(T)));
-            else
-                out[x][v] = ld<POL == 1>(row + vc);
+            out[x][v] = ld<POL == 1>(row + vc);
         }
     }
 #pragma unroll
@@ -456,7 +444,7 @@ __global__ __launch_bounds__(kBlock) void k_sgd_batch(SgdArgs<T> A) {
     }
     VT p[S][V], q[S][V];
     if (kv > 0) {
-        gather_rows<T, W, GS, V, S, POL>(A.P, uu, k, kv, l, p, A.p_bytes);
+        gather_rows<T, W, GS, V, S, POL>(A.P, uu, k, kv, l, p);
         gather_rows<T, W, GS, V, S, 0>(A.Q, ii, k, kv, l, q);
     } else {
 #pragma unroll
@@ -484,22 +472,13 @@ __global__ __launch_bounds__(kBlock) void k_sgd_batch(SgdArgs<T> A) {
         }
         VT* pw = reinterpret_cast<VT*>(A.P + (int64_t)uu[x] * k);
         VT* qw = reinterpret_cast<VT*>(A.Q + (int64_t)ii[x] * k);
-        [[maybe_unused]] __amdgpu_buffer_rsrc_t prs;
-        if constexpr (POL >= 2) prs = buf_rsrc(A.P, A.p_bytes);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const int vi = v * GS + l;
             if (!(have[x] && vi < kv)) continue;
             VT np, nq;
             sgd_rows<T, KERN>(p[x][v], q[x][v], e, d, h, np, nq);
-            if constexpr (POL >= 2) {
-                if (A.upd_user)
-                    buf_st<kPolAux[POL].st>(
-                        prs, (uint32_t)(((uint32_t)uu[x] * (uint32_t)k + (uint32_t)(vi * W)) * sizeof(T)),
-                        np);
-            } else {
-                if (A.upd_user) st<NT>(pw + vi, np);
-            }
+            if (A.upd_user) st<NT>(pw + vi, np);
             if (A.upd_item) qw[vi] = nq;
         }
     }
@@ -601,163 +580,37 @@ __global__ __launch_bounds__(kBlock) void k_sse_stream(ReadArgs<T> A, SliceTab S
 // of its slice is cut into R contiguous runs, one per group of GS lanes; in
 // mf_sched_slices order a run is user-major (a user has ~nnz/(n_users *
 // slices) consecutive ratings in a slice), so a group loads a user's P row
-// and bias once per run of that user and only the item row per rating: the
+// once per run of that user and only the item row per rating: the
 // vector-memory instructions per rating drop from two row loads to one plus
 // the rare user change.  Each group walks its run S ratings per step; the
 // triples come in chunks of GS per group (lane l of group g holds rating
 // r0 + c + l), prefetched one chunk ahead.
-template <typename T, int W, int GS, int V, int KERN, int S>
-__global__ __launch_bounds__(kBlock) void k_sse_owned(ReadArgs<T> A, SliceTab SL) {
-    using VT = typename VecOf<T, W>::type;
-    constexpr int R = kWave / GS;
-    static_assert(GS % S == 0, "a chunk of GS ratings is whole steps");
-    const int lane = threadIdx.x & (kWave - 1);
-    const int g = lane / GS;
-    const int l = lane % GS;
-    const int k = A.k;
-    const int kv = k / W;
-    const Hyper<T> h = A.h;
-    const SliceWave sw = slice_wave(SL);
-    const int x_slice = sw.x;
-    const int64_t nw_slice = sw.nw;
-    const int64_t wv = sw.wv;
-    const int64_t s0 = SL.off[x_slice], len = SL.off[x_slice + 1] - s0;
-    const int64_t b0 = s0 + len * wv / nw_slice;
-    const int64_t b1 = s0 + len * (wv + 1) / nw_slice;
-    double acc = 0.0;
-    if (b0 < b1) {
-        const int64_t wl = b1 - b0;
-        const int64_t r0 = b0 + wl * g / R, r1 = b0 + wl * (g + 1) / R;   // this group's run
-        const int64_t maxrun = (wl + R - 1) / R;                          // wave-uniform trips
-        const int64_t last = r1 > r0 ? r1 - 1 : b0;
-        const __amdgpu_buffer_rsrc_t rp = buf_rsrc(A.P, A.p_bytes), rq = buf_rsrc(A.Q, A.q_bytes);
-        const __amdgpu_buffer_rsrc_t rbu = buf_rsrc(A.Bu, A.bu_bytes), rbi = buf_rsrc(A.Bi, A.bi_bytes);
-        auto fetch = [&](int64_t c, int& u, int& i, T& r) {
-            const int64_t j = min(r0 + c + l, last);
-            u = A.u[j]; i = A.i[j]; r = A.r[j];
-        };
-        int nu_, ni_;
-        T nr_;
-        fetch(0, nu_, ni_, nr_);
-        int pu = -1;                       // user whose row is held in pp / pbu
-        VT pp[V];
-        T pbu = (T)0;
-#pragma unroll
-        for (int v = 0; v < V; ++v) pp[v] = (VT)(T)0;
-        for (int64_t c = 0; c < maxrun; c += GS) {
-            const int tu = nu_, ti = ni_;
-            const T tr = nr_;
-            if (c + GS < maxrun) fetch(c + GS, nu_, ni_, nr_);          // prefetch
-#pragma unroll 1
-            for (int t = 0; t < GS; t += S) {
-                int uu[S], ii[S];
-                T rr[S];
-                bool hv[S], need[S];
-#pragma unroll
-                for (int x = 0; x < S; ++x) {
-                    const int src = g * GS + t + x;
-                    uu[x] = take_i<GS>(tu, src);
-                    ii[x] = take_i<GS>(ti, src);
-                    rr[x] = take_f<GS>(tr, src);
-                    hv[x] = r0 + c + t + x < r1;
-                }
-#pragma unroll
-                for (int x = 0; x < S; ++x) need[x] = uu[x] != (x == 0 ? pu : uu[x - 1]);
-                // Branch-free loads: item rows for every rating, user rows as
-                // buffer loads whose offset is out of range (returns 0, no
-                // memory access) where the run stays on the same user.
-                VT q[S][V], p[S][V];
-                T bi[S], bu[S];
-#pragma unroll
-                for (int x = 0; x < S; ++x) {
-#pragma unroll
-                    for (int v = 0; v < V; ++v) {
-                        const int vi = v * GS + l;
-                        const int vc = vi < kv ? vi : kv - 1;
-                        q[x][v] = buf_ld<0, VT>(rq, (uint32_t)(((uint32_t)ii[x] * (uint32_t)k +
-                                                               (uint32_t)(vc * W)) * sizeof(T)));
-                        const uint32_t po = need[x] ? (uint32_t)(((uint32_t)uu[x] * (uint32_t)k +
-                                                                   (uint32_t)(vc * W)) * sizeof(T))
-                                                    : 0xFFFFFFF0u;
-                        // skipped by the whole wave when no group changes user
-                        if (__builtin_amdgcn_ballot_w64(need[x]) != 0)
-                            p[x][v] = buf_ld<0, VT>(rp, po);
-                        else
-                            p[x][v] = (VT)(T)0;
-                    }
-                    if constexpr (KERN != MF_RBF) {
-                        bi[x] = buf_ld<0, T>(rbi, (uint32_t)ii[x] * (uint32_t)sizeof(T));
-                        bu[x] = buf_ld<0, T>(rbu, need[x] ? (uint32_t)uu[x] * (uint32_t)sizeof(T)
-                                                          : 0xFFFFFFF0u);
-                    } else {
-                        bi[x] = bu[x] = (T)0;
-                    }
-                }
-                // the user row of each rating: loaded, or carried from the
-                // previous rating of the run
-#pragma unroll
-                for (int x = 0; x < S; ++x) {
-#pragma unroll
-                    for (int v = 0; v < V; ++v) p[x][v] = need[x] ? p[x][v] : (x == 0 ? pp[v] : p[x - 1][v]);
-                    bu[x] = need[x] ? bu[x] : (x == 0 ? pbu : bu[x - 1]);
-                }
-#pragma unroll
-                for (int x = 0; x < S; ++x) {
-                    T part = (T)0;
-#pragma unroll
-                    for (int v = 0; v < V; ++v) {
-                        VT pv[1] = {p[x][v]}, qv[1] = {q[x][v]};
-                        const T pt = lane_partial<T, W, 1, KERN>(pv, qv);
-                        part += v * GS + l < kv ? pt : (T)0;
-                    }
-                    const T sm = group_sum<GS>(part);
-                    const T err = rr[x] - predict_one<T, KERN>(sm, bu[x], bi[x], h);   // :313
-                    if (hv[x] && l == 0) acc += (double)err * (double)err;
-                }
-#pragma unroll
-                for (int v = 0; v < V; ++v) pp[v] = p[S - 1][v];
-                pbu = bu[S - 1];
-                pu = uu[S - 1];
-            }
-        }
-    }
-    acc = wave_sum(acc);
-    __shared__ double red[kWavesPerBlock];
-    if (lane == 0) red[threadIdx.x / kWave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kWavesPerBlock; ++w) t += red[w];
-        A.partials[blockIdx.x] = t;
-    }
-}
-
-// Training SSE, k_sse_owned's walk with fewer VALU instructions per rating
-// (the pass is VALU-issue bound: 10.4 VALU wave-instructions per rating at
-// C3, PMC r02h, about 1.7 of its 2.3 ms).  Same ratings per wave, same owned
-// user rows, same per-rating arithmetic and the same FP64 sum, bit for bit:
+//
+// The pass is VALU-issue bound (10.4 VALU wave-instructions per rating at
+// C3, PMC r02h, about 1.7 of its 2.3 ms), so the walk is written for few
+// VALU instructions per rating:
 //  * row offsets as one v_mad_u32_u24 where every id < 2^24 (U24) instead of
 //    the quarter-rate v_mul_lo_u32 + shift;
-//  * the user row and user bias are loaded only inside the wave-uniform
-//    "some group changes user" branch; no zero-fill of skipped slots (their
-//    registers are never selected), one carried row instead of S copies;
+//  * the user row is loaded only inside the wave-uniform "some group changes
+//    user" branch (a lane that keeps its user reads past the resource: zero,
+//    no memory access); no zero-fill of skipped slots (their registers are
+//    never selected), one carried row instead of S copies;
 //  * the dot product starts from the first product (0 + x = x up to the
 //    sign of zero, which err^2 does not see); rows without a tail (k ==
 //    GS V W) skip the per-vector masks;
 //  * live ratings counted in int32 per step; the FP64 square-add of FP32
 //    errors as one v_fma_f64 (err^2 is exact in FP64, so fma == mul + add)
-//    of an error zeroed on idle slots and on non-lead lanes.
-// The walk of k_sse_lean over one wave's share [b0, b1) of the evaluation
-// order; returns the lane's part of the FP64 SSE (non-lead lanes: 0).
-// BC (bias per chunk): the item and user biases of a chunk's GS ratings are
-// loaded ONE per lane when the chunk starts (lane l holds rating c + l's) and
-// handed to each rating's step by the same lane broadcast as its rating --
-// instead of one wave-wide load per rating and step (S + the user-change
-// loads per step: FP32 rank 64 issued as many bias loads as row loads,
-// 16 + 16 per step), which cost the texture path (TA) an instruction each
-// for 8 or 4 bytes.  Same values, same arithmetic, bit for bit.
-template <typename T, int W, int GS, int V, int KERN, int S, bool U24, bool BC = true>
+//    of an error zeroed on idle slots and on non-lead lanes;
+//  * the item and user biases of a chunk's GS ratings are loaded ONE per
+//    lane when the chunk starts (lane l holds rating c + l's) and handed to
+//    each rating's step by the same lane broadcast as its rating -- one
+//    wave-wide load per rating and step (FP32 rank 64: as many bias loads as
+//    row loads, 16 + 16 per step) cost the texture path (TA) an instruction
+//    each for 8 or 4 bytes.
+// sse_lean_range is the walk of k_sse_lean over one wave's share [b0, b1) of
+// the evaluation order; it returns the lane's part of the FP64 SSE (non-lead
+// lanes: 0).
+template <typename T, int W, int GS, int V, int KERN, int S, bool U24>
 __device__ __forceinline__ double sse_lean_range(const ReadArgs<T>& A, int64_t b0, int64_t b1) {
     using VT = typename VecOf<T, W>::type;
     constexpr int R = kWave / GS;
@@ -809,10 +662,10 @@ __device__ __forceinline__ double sse_lean_range(const ReadArgs<T>& A, int64_t b
             for (int64_t c = 0; c < maxrun; c += GS) {
                 const int tu = nu_, ti = ni_;
                 const T tr = nr_;
-                // BC: the chunk's biases, one per lane (issued before the
+                // the chunk's biases, one per lane (issued before the
                 // prefetch: the counter waits for them do not wait for it)
                 [[maybe_unused]] T tbi = (T)0, tbu = (T)0;
-                if constexpr (BC && KERN != MF_RBF) {
+                if constexpr (KERN != MF_RBF) {
                     tbi = buf_ld<0, T>(rbi, (uint32_t)ti * (uint32_t)sizeof(T));
                     tbu = buf_ld<0, T>(rbu, (uint32_t)tu * (uint32_t)sizeof(T));
                 }
@@ -842,12 +695,7 @@ __device__ __forceinline__ double sse_lean_range(const ReadArgs<T>& A, int64_t b
                             const int vc = FULL || vi < kv ? vi : kv - 1;
                             q[x][v] = buf_ld<0, VT>(rq, row_off(ii[x], vc));
                         }
-                        if constexpr (KERN != MF_RBF) {
-                            if constexpr (BC)
-                                bi[x] = take_f<GS>(tbi, g * GS + t + x);
-                            else
-                                bi[x] = buf_ld<0, T>(rbi, (uint32_t)ii[x] * (uint32_t)sizeof(T));
-                        }
+                        if constexpr (KERN != MF_RBF) bi[x] = take_f<GS>(tbi, g * GS + t + x);
                         // wave-uniform: skipped unless some group changes user
                         // here; a lane that keeps its user reads out of range
                         if (__builtin_amdgcn_ballot_w64(need[x]) != 0) {
@@ -857,11 +705,8 @@ __device__ __forceinline__ double sse_lean_range(const ReadArgs<T>& A, int64_t b
                                 const int vc = FULL || vi < kv ? vi : kv - 1;
                                 pl[x][v] = buf_ld<0, VT>(rp, need[x] ? row_off(uu[x], vc) : kBufDropRd);
                             }
-                            if constexpr (KERN != MF_RBF && !BC)
-                                bul[x] = buf_ld<0, T>(rbu, need[x] ? (uint32_t)uu[x] * (uint32_t)sizeof(T)
-                                                                   : kBufDropRd);
                         }
-                        if constexpr (KERN != MF_RBF && BC) bul[x] = take_f<GS>(tbu, g * GS + t + x);
+                        if constexpr (KERN != MF_RBF) bul[x] = take_f<GS>(tbu, g * GS + t + x);
                     }
 #pragma unroll
                     for (int x = 0; x < S; ++x) {
@@ -909,186 +754,13 @@ __device__ __forceinline__ void sse_block_partial(double acc, double* partials) 
     }
 }
 
-template <typename T, int W, int GS, int V, int KERN, int S, bool U24, bool BC = true>
+template <typename T, int W, int GS, int V, int KERN, int S, bool U24>
 __global__ __launch_bounds__(kBlock) void k_sse_lean(ReadArgs<T> A, SliceTab SL) {
     const SliceWave sw = slice_wave(SL);
     const int64_t s0 = SL.off[sw.x], len = SL.off[sw.x + 1] - s0;
     const int64_t b0 = s0 + len * sw.wv / sw.nw;
     const int64_t b1 = s0 + len * (sw.wv + 1) / sw.nw;
-    sse_block_partial(sse_lean_range<T, W, GS, V, KERN, S, U24, BC>(A, b0, b1), A.partials);
-}
-
-// Training SSE over TILES walked in phases by a resident grid (the FP64
-// pass; DESIGN.md section 5, "FP64 RMSE pass").  The evaluation order is
-// cut into n = 8 P tiles (mf_sched_tiles: user chunk c x item slice s,
-// tile c * S + s, users ascending inside a tile); phase ph = tile / 8 and
-// block b walks, phase after phase, its share of tile 8 ph + (b mod 8).
-// With one block per resident slot every block of an XCD (b mod 8 under
-// the observed round-robin placement -- speed only) is in about the same
-// phase at the same time, so the XCD's L2 serves one item slice (and one
-// user chunk's rows) instead of the several a dispatch-ordered grid has in
-// flight.  Same ratings per wave-share, same per-rating arithmetic and the
-// same FP64 sum per lane as k_sse_lean.
-template <typename T, int W, int GS, int V, int KERN, int S, bool U24>
-__global__ __launch_bounds__(kBlock) void k_sse_phased(ReadArgs<T> A, SliceTab SL) {
-    const int64_t per_x = gridDim.x / 8;                        // blocks per XCD
-    const int64_t nw = per_x * kWavesPerBlock;
-    const int64_t wv = (int64_t)(blockIdx.x / 8) * kWavesPerBlock + threadIdx.x / kWave;
-    const int xb = (int)(blockIdx.x % 8);
-    double acc = 0.0;
-    for (int ph = 0; ph < SL.n / 8; ++ph) {
-        const int x = 8 * ph + xb;
-        const int64_t s0 = SL.off[x], len = SL.off[x + 1] - s0;
-        acc += sse_lean_range<T, W, GS, V, KERN, S, U24>(A, s0 + len * wv / nw,
-                                                          s0 + len * (wv + 1) / nw);
-    }
-    sse_block_partial(acc, A.partials);
-}
-
-
-// Training SSE, software-pipelined form of k_sse_owned (same ratings, same
-// owned user rows, same per-rating arithmetic).  A group's run is cut into
-// chunks of GS ratings (the triples of a chunk arrive in the group's GS
-// lanes) and a chunk into Q = GS / S pieces of S ratings; the loads of piece
-// j+1 are in flight while piece j is reduced (two register sets A / B used
-// alternately, so no in-flight register is ever copied).  Every load is
-// issued unconditionally -- the user row of a rating whose user the run
-// already holds is a buffer load past the resource (kBufRowDrop: dropped, no
-// memory access) -- so the compiler's waits count exactly the other set's
-// loads.
-constexpr uint32_t kBufRowDrop = 0xFFFFFFF0u;
-
-template <typename T, int W, int GS, int V, int KERN, int S>
-__global__ __launch_bounds__(kBlock) void k_sse_pipe(ReadArgs<T> A, SliceTab SL) {
-    using VT = typename VecOf<T, W>::type;
-    constexpr int R = kWave / GS;
-    constexpr int Q = GS / S;
-    static_assert(GS % S == 0 && Q % 2 == 0, "a chunk is an even number of pieces");
-    const int lane = threadIdx.x & (kWave - 1);
-    const int g = lane / GS;
-    const int l = lane % GS;
-    const int k = A.k;
-    const int kv = k / W;
-    const Hyper<T> h = A.h;
-    const SliceWave sw = slice_wave(SL);
-    const int x_slice = sw.x;
-    const int64_t nw_slice = sw.nw;
-    const int64_t wv = sw.wv;
-    const int64_t s0 = SL.off[x_slice], len = SL.off[x_slice + 1] - s0;
-    const int64_t b0 = s0 + len * wv / nw_slice;
-    const int64_t b1 = s0 + len * (wv + 1) / nw_slice;
-    double acc = 0.0;
-    if (b0 < b1) {
-        const int64_t wl = b1 - b0;
-        const int64_t r0 = b0 + wl * g / R, r1 = b0 + wl * (g + 1) / R;   // this group's run
-        const int64_t maxrun = (wl + R - 1) / R;                          // wave-uniform trips
-        const int64_t last = r1 > r0 ? r1 - 1 : b0;
-        const __amdgpu_buffer_rsrc_t rp = buf_rsrc(A.P, A.p_bytes), rq = buf_rsrc(A.Q, A.q_bytes);
-        const __amdgpu_buffer_rsrc_t rbu = buf_rsrc(A.Bu, A.bu_bytes), rbi = buf_rsrc(A.Bi, A.bi_bytes);
-        struct Tri { int u, i; T r; };
-        struct Piece {
-            int uu[S];
-            bool hv[S], need[S];
-            T rr[S], bi[S], bu[S];
-            VT q[S][V], p[S][V];
-        };
-        auto fetch = [&](int64_t c, Tri& t) __attribute__((always_inline)) {
-            const int64_t j = min(r0 + c + l, last);
-            t.u = A.u[j]; t.i = A.i[j]; t.r = A.r[j];
-        };
-        int lastu = -1;                    // user of the last rating issued by this group
-        // issue the loads of piece `pc` of the chunk at run offset c (triples tr)
-        auto issue = [&](const Tri& tr, int64_t c, int pc, Piece& o) __attribute__((always_inline)) {
-            int ii[S];
-#pragma unroll
-            for (int x = 0; x < S; ++x) {
-                const int src = g * GS + pc * S + x;
-                o.uu[x] = take_i<GS>(tr.u, src);
-                ii[x] = take_i<GS>(tr.i, src);
-                o.rr[x] = take_f<GS>(tr.r, src);
-                o.hv[x] = r0 + c + pc * S + x < r1;
-            }
-#pragma unroll
-            for (int x = 0; x < S; ++x) o.need[x] = o.uu[x] != (x == 0 ? lastu : o.uu[x - 1]);
-            lastu = o.uu[S - 1];
-#pragma unroll
-            for (int x = 0; x < S; ++x) {
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    const int vi = v * GS + l;
-                    const int vc = vi < kv ? vi : kv - 1;
-                    o.q[x][v] = buf_ld<0, VT>(rq, (uint32_t)(((uint32_t)ii[x] * (uint32_t)k +
-                                                             (uint32_t)(vc * W)) * sizeof(T)));
-                    o.p[x][v] = buf_ld<0, VT>(
-                        rp, o.need[x] ? (uint32_t)(((uint32_t)o.uu[x] * (uint32_t)k +
-                                                    (uint32_t)(vc * W)) * sizeof(T))
-                                      : kBufRowDrop);
-                }
-                if constexpr (KERN != MF_RBF) {
-                    o.bi[x] = buf_ld<0, T>(rbi, (uint32_t)ii[x] * (uint32_t)sizeof(T));
-                    o.bu[x] = buf_ld<0, T>(rbu, o.need[x] ? (uint32_t)o.uu[x] * (uint32_t)sizeof(T)
-                                                          : kBufRowDrop);
-                } else {
-                    o.bi[x] = o.bu[x] = (T)0;
-                }
-            }
-        };
-        VT pp[V];                          // row / bias of the run's current user
-        T pbu = (T)0;
-#pragma unroll
-        for (int v = 0; v < V; ++v) pp[v] = (VT)(T)0;
-        auto consume = [&](Piece& o) __attribute__((always_inline)) {
-#pragma unroll
-            for (int x = 0; x < S; ++x) {
-#pragma unroll
-                for (int v = 0; v < V; ++v)
-                    o.p[x][v] = o.need[x] ? o.p[x][v] : (x == 0 ? pp[v] : o.p[x - 1][v]);
-                o.bu[x] = o.need[x] ? o.bu[x] : (x == 0 ? pbu : o.bu[x - 1]);
-            }
-#pragma unroll
-            for (int x = 0; x < S; ++x) {
-                T part = (T)0;
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    VT pv[1] = {o.p[x][v]}, qv[1] = {o.q[x][v]};
-                    const T pt = lane_partial<T, W, 1, KERN>(pv, qv);
-                    part += v * GS + l < kv ? pt : (T)0;
-                }
-                const T sm = group_sum<GS>(part);
-                const T err = o.rr[x] - predict_one<T, KERN>(sm, o.bu[x], o.bi[x], h);   // :313
-                if (o.hv[x] && l == 0) acc += (double)err * (double)err;
-            }
-#pragma unroll
-            for (int v = 0; v < V; ++v) pp[v] = o.p[S - 1][v];
-            pbu = o.bu[S - 1];
-        };
-        Tri tc, tn;
-        Piece pa, pb;
-        fetch(0, tc);
-        issue(tc, 0, 0, pa);
-        for (int64_t c = 0; c < maxrun; c += GS) {
-            fetch(c + GS, tn);             // the next chunk's triples
-#pragma unroll
-            for (int j = 0; j < Q; j += 2) {
-                issue(tc, c, j + 1, pb);
-                consume(pa);
-                if (j + 2 < Q) issue(tc, c, j + 2, pa);
-                else issue(tn, c + GS, 0, pa);     // past the run: clamped, hv false
-                consume(pb);
-            }
-            tc = tn;
-        }
-    }
-    acc = wave_sum(acc);
-    __shared__ double red[kWavesPerBlock];
-    if (lane == 0) red[threadIdx.x / kWave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kWavesPerBlock; ++w) t += red[w];
-        A.partials[blockIdx.x] = t;
-    }
+    sse_block_partial(sse_lean_range<T, W, GS, V, KERN, S, U24>(A, b0, b1), A.partials);
 }
 
 // Training SSE with the ITEM rows stationary in LDS and the user rows
@@ -1369,7 +1041,6 @@ struct SgdParams {
     double gamma, lr, reg, lo, hi; int32_t uu, ui, flags;
     hipStream_t stream; double* kernel_ms;
     int32_t* claim;         // nullable: nl x 8 tile counters (zeroed here)
-    int64_t n_users;
 };
 
 struct SseParams {
@@ -1388,42 +1059,16 @@ template <typename T>
 struct SgdRun {
     const SgdParams& p;
 
-    // flags bits 8..11: experimental slot count for the rank-64 FP32 layout
-    // flags bits 8..11: experimental slot count, bits 12..15: experimental
-    // user-row policy (kPolAux), both for the rank-64 FP32 linear layout only
+    // the user rows, biases and triples of a batch: non-temporal ops under
+    // MF_FLAG_NT_USER (k_sgd_batch's POL 1), plain ones otherwise
     template <int W, int GS, int V, int KERN>
     int run() {
-        constexpr int SD = SlotsFor<kWave / GS, V, W>::S;
-        const bool nt = (p.flags & MF_FLAG_NT_USER) != 0;
-        if constexpr (std::is_same<T, float>::value && W == 4 && GS == 16 && V == 1) {
-            switch ((p.flags >> 8) & 0xf) {
-                case 1: return nt ? go<W, GS, V, KERN, 2, 1>() : go<W, GS, V, KERN, 2, 0>();
-                case 2: return nt ? go<W, GS, V, KERN, 8, 1>() : go<W, GS, V, KERN, 8, 0>();
-                case 3: return nt ? go<W, GS, V, KERN, 1, 1>() : go<W, GS, V, KERN, 1, 0>();
-                default: break;
-            }
-            if constexpr (KERN == MF_LINEAR) {
-                const int pol = (p.flags >> 12) & 0xf;
-                if (pol >= 2 && (uint64_t)p.n_users * (uint64_t)p.k * sizeof(T) > 0xFFFFFFFFull) {
-                    set_error("user-row policy %d needs P < 4 GiB", pol);
-                    return MF_ERR_INVALID;
-                }
-                switch (pol) {
-                    case 2: return go<W, GS, V, KERN, SD, 2>();
-                    case 3: return go<W, GS, V, KERN, SD, 3>();
-                    case 4: return go<W, GS, V, KERN, SD, 4>();
-                    case 5: return go<W, GS, V, KERN, SD, 5>();
-                    case 6: return go<W, GS, V, KERN, SD, 6>();
-                    case 7: return go<W, GS, V, KERN, SD, 7>();
-                    default: break;
-                }
-            }
-        }
-        return nt ? go<W, GS, V, KERN, SD, 1>() : go<W, GS, V, KERN, SD, 0>();
+        return (p.flags & MF_FLAG_NT_USER) ? go<W, GS, V, KERN, 1>() : go<W, GS, V, KERN, 0>();
     }
 
-    template <int W, int GS, int V, int KERN, int S, int POL>
+    template <int W, int GS, int V, int KERN, int POL>
     int go() {
+        constexpr int S = SlotsFor<kWave / GS, V, W>::S;
         constexpr int RPW = S * (kWave / GS);
         SgdArgs<T> a;
         a.u = p.u; a.i = p.i; a.r = static_cast<const T*>(p.r); a.order = p.order;
@@ -1432,7 +1077,6 @@ struct SgdRun {
         a.k = p.k; a.upd_user = p.uu; a.upd_item = p.ui;
         a.swizzle = (p.flags & MF_FLAG_XCD_SWIZZLE) ? 1 : 0;
         a.claim = nullptr;
-        a.p_bytes = (uint64_t)p.n_users * (uint64_t)p.k * sizeof(T);
         a.h = make_hyper<T>(p.mu, p.lr, p.reg, p.gamma, p.lo, p.hi);
         if (p.claim) MF_HIP_CHECK(hipMemsetAsync(p.claim, 0, sizeof(int32_t) * 8 * (size_t)p.nl,
                                                  p.stream));
@@ -1503,68 +1147,28 @@ struct SseRun {
         a.Bu = static_cast<const T*>(p.bu); a.Bi = static_cast<const T*>(p.bi);
         a.n = p.n; a.k = p.k; a.bound = 0; a.out = nullptr; a.partials = p.partials;
         a.h = make_hyper<T>(p.mu, 0.0, 0.0, p.gamma, p.lo, p.hi);
-        // Up to eight workgroups per resident slot, each an equal share of
-        // its slice, but at least ~6K ratings per wave: the shorter shares
-        // even out the per-wave rate differences on large inputs (C3, rank
-        // 64: 2.45 ms with one share per resident slot, 2.26 / 2.25 / 2.24 ms
-        // with 2048 / 4096 / 8192 workgroups; tools/sse_probe.py), while on
-        // small ones (C2, the N=8 shard) more workgroups only add tail
-        // (0.094 -> 0.105 ms, 0.276 -> 0.286 ms at 8 per slot).
-        // MF_SSE_BLOCKS overrides (probes).
         a.p_bytes = (uint64_t)p.n_users * p.k * sizeof(T);
         a.q_bytes = (uint64_t)p.n_items * p.k * sizeof(T);
         a.bu_bytes = (uint64_t)p.n_users * sizeof(T);
         a.bi_bytes = (uint64_t)p.n_items * sizeof(T);
-        // k_sse_owned (default); MF_SSE_VARIANT=1 selects k_sse_stream (probes,
-        // tools/sse_probe.py) and so does a P or Q too large for a buffer
-        // resource.  Measured at C3 (rank 64, FP32): 2.49 vs 2.66 ms; the
-        // owned kernel without the wave-uniform skip of user-row loads took
-        // 2.72 ms, with non-temporal user streams 2.69 ms.
-        // k_sse_lean (default; the ids-below-2^24 form where they are) and,
-        // as probes (MF_SSE_VARIANT): 6 = k_sse_owned, the round-2 default.
+        // k_sse_lean, in its ids-below-2^24 form where they are; k_sse_stream
+        // where P or Q is too large for a buffer resource.  MF_SSE_VARIANT=1
+        // also selects k_sse_stream: the hook that lets a test reach the
+        // >= 4 GiB fallback at a small size (any other value: the default).
+        // Measured at C3 (rank 64, FP32), owned user rows against the
+        // stream: 2.49 vs 2.66 ms.
+        // FP32 rows of one vector per lane (rank 64) take a whole chunk of 16
+        // ratings per group per step (C3: 2.45 vs 2.52 ms with 4, 2.46 with 8).
+        constexpr int SL = GS == 16 && V == 1 && std::is_same<T, float>::value ? 16 : S;
+        enum { kLean24, kLeanWide, kStream, kForms };
         const char* ev = std::getenv("MF_SSE_VARIANT");
-        int var = ev && std::atoi(ev) == 1 ? 1 : 0;
-        if (a.p_bytes >= (1ull << 32) - 64 || a.q_bytes >= (1ull << 32) - 64) var = 1;  // buffer range
-        const bool u24 = p.n_users < (1 << 24) && p.n_items < (1 << 24);
-        auto kfn = var == 1 ? k_sse_stream<T, W, GS, V, KERN, S>
-                 : u24      ? k_sse_lean<T, W, GS, V, KERN, S, true>
-                            : k_sse_lean<T, W, GS, V, KERN, S, false>;
-        if (var == 0 && ev && std::atoi(ev) == 6) { var = 6; kfn = k_sse_owned<T, W, GS, V, KERN, S>; }
-        // probe: 12 = the round-5 k_sse_lean (a bias load per rating and step)
-        if (var == 0 && u24 && ev && std::atoi(ev) == 12) {
-            var = 12;
-            kfn = k_sse_lean<T, W, GS, V, KERN, S, true, false>;
-            if constexpr (GS == 16 && V == 1 && std::is_same<T, float>::value)
-                kfn = k_sse_lean<T, W, GS, V, KERN, 16, true, false>;
-        }
-        // FP32 rows of one vector per lane (rank 64): a whole chunk of 16
-        // ratings per group per step (C3: 2.45 vs 2.52 ms with S = 4, 2.46
-        // with 8; tools/sse_probe.py).  Probes: 2 = 8 per step, 3 = SlotsFor.
-        if constexpr (GS == 16 && V == 1 && std::is_same<T, float>::value) {
-            if (var == 0) kfn = u24 ? k_sse_lean<T, W, GS, V, KERN, 16, true>
-                                    : k_sse_lean<T, W, GS, V, KERN, 16, false>;
-            if (var == 6) kfn = k_sse_owned<T, W, GS, V, KERN, 16>;
-            if (var == 0 && u24 && ev && std::atoi(ev) == 8) { var = 8; kfn = k_sse_lean<T, W, GS, V, KERN, 8, true>; }
-            if (var == 0 && u24 && ev && std::atoi(ev) == 9) { var = 9; kfn = k_sse_lean<T, W, GS, V, KERN, 4, true>; }
-            if (var == 0 && ev && std::atoi(ev) == 2) { var = 2; kfn = k_sse_owned<T, W, GS, V, KERN, 8>; }
-            if (var == 0 && ev && std::atoi(ev) == 3) { var = 3; kfn = k_sse_owned<T, W, GS, V, KERN, S>; }
-            if (var == 0 && ev && std::atoi(ev) == 4) { var = 4; kfn = k_sse_pipe<T, W, GS, V, KERN, 8>; }
-            if (var == 0 && ev && std::atoi(ev) == 5) { var = 5; kfn = k_sse_pipe<T, W, GS, V, KERN, 4>; }
-        }
-        // tiles walked in phases by a resident grid (mf_sched_tiles order:
-        // n > 8, a multiple of 8); MF_SSE_PHASED=0 walks them as a
-        // dispatch-ordered grid (slice_wave) instead
-        const char* ep = std::getenv("MF_SSE_PHASED");
-        const bool phased = var == 0 && p.S.n > 8 && p.S.n % 8 == 0 && !(ep && ep[0] == '0');
-        if (phased) {
-            var = u24 ? 10 : 11;
-            kfn = u24 ? k_sse_phased<T, W, GS, V, KERN, S, true>
-                      : k_sse_phased<T, W, GS, V, KERN, S, false>;
-            if constexpr (GS == 16 && V == 1 && std::is_same<T, float>::value)
-                kfn = u24 ? k_sse_phased<T, W, GS, V, KERN, 16, true>
-                          : k_sse_phased<T, W, GS, V, KERN, 16, false>;
-        }
-        if (var == 0 && !u24) var = 7;                    // its own occupancy entry
+        const bool big = a.p_bytes >= (1ull << 32) - 64 || a.q_bytes >= (1ull << 32) - 64;
+        const int var = big || (ev && std::atoi(ev) == 1)                 ? kStream
+                      : p.n_users < (1 << 24) && p.n_items < (1 << 24)    ? kLean24
+                                                                          : kLeanWide;
+        const auto kfn = var == kStream ? k_sse_stream<T, W, GS, V, KERN, S>
+                       : var == kLean24 ? k_sse_lean<T, W, GS, V, KERN, SL, true>
+                                        : k_sse_lean<T, W, GS, V, KERN, SL, false>;
         if (p.attrs_out) {
             hipFuncAttributes fa;
             MF_HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kfn)));
@@ -1573,7 +1177,7 @@ struct SseRun {
             p.attrs_out[2] = (int32_t)fa.sharedSizeBytes;
             return MF_OK;
         }
-        static int resident_tab[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // per instantiation and variant
+        static int resident_tab[kForms] = {0, 0, 0};      // per instantiation and form
         int& resident = resident_tab[var];
         if (resident == 0) {
             const LaunchTrace lt;
@@ -1588,24 +1192,20 @@ struct SseRun {
                 resident = kSseMaxBlocks;
             lt.mark("sse occupancy");
         }
+        // Up to eight workgroups per resident slot, each an equal share of
+        // its slice, but at least ~6K ratings per wave: the shorter shares
+        // even out the per-wave rate differences on large inputs (C3, rank
+        // 64: 2.45 ms with one share per resident slot, 2.26 / 2.25 / 2.24 ms
+        // with 2048 / 4096 / 8192 workgroups), while on small ones (C2, the
+        // N=8 shard) more workgroups only add tail (0.094 -> 0.105 ms,
+        // 0.276 -> 0.286 ms at 8 per slot).
         constexpr int64_t kSseRatingsPerWave = 6144;
         const int64_t by_size = p.n / (kSseRatingsPerWave * kWavesPerBlock);
         int blocks = (int)std::min<int64_t>(
             std::max<int64_t>(resident, std::min<int64_t>(by_size, 8 * (int64_t)resident)),
             kSseMaxBlocks);
-        // phased: one block per resident slot (all of an XCD's blocks move
-        // through the phases together)
-        if (phased) blocks = std::min(resident, kSseMaxBlocks);
-        if (const char* e = std::getenv("MF_SSE_BLOCKS")) {
-            const int v = std::atoi(e);
-            if (v > 0) blocks = std::min(v, kSseMaxBlocks);
-        }
         if (p.max_blocks > 0) blocks = std::min(blocks, p.max_blocks);
-        if (phased) {
-            blocks = std::max(8, (blocks / 8) * 8);      // a multiple of 8
-        } else {
-            blocks = std::max(p.S.n, (blocks / p.S.n) * p.S.n);
-        }
+        blocks = std::max(p.S.n, (blocks / p.S.n) * p.S.n);    // whole shares per slice
         const LaunchTrace lt2;
         hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kBlock), 0, p.stream, a, p.S);
         hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(kBlock), 0, p.stream,

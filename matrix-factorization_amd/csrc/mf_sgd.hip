@@ -1,6 +1,6 @@
 // mf_sgd.hip -- C ABI of the KernelMF hot path (include/mf_hip.h):
 //   mf_sgd_epoch  -> k_sgd_batch  (mf_rows.hpp; one launch per batch)
-//   mf_sse        -> k_sse_owned (mf_rows.hpp)
+//   mf_sse        -> k_sse_lean  (mf_rows.hpp)
 //   mf_predict    -> k_read       (this file)
 //
 // Compiled with -ffp-contract=off: every scalar expression rounds like the
@@ -24,7 +24,7 @@ template <typename T, int V> struct Tile {
 
 // Batched prediction (_predict, kernel_matrix_factorization.py:448-541):
 // -1 ids read as a zero bias and an all-zero factor row (:487-499).
-template <typename T, int GS, int V, int KERN, bool SSE>
+template <typename T, int GS, int V, int KERN>
 __global__ __launch_bounds__(kBlock) void k_read(ReadArgs<T> A, SliceTab S) {
     constexpr int R = kWave / GS;
     constexpr int U = Tile<T, V>::U;
@@ -39,7 +39,6 @@ __global__ __launch_bounds__(kBlock) void k_read(ReadArgs<T> A, SliceTab S) {
     const int64_t s_end = S.off[x_slice + 1];
     const int64_t nwaves = bps * kWavesPerBlock;
     const int64_t wave = (int64_t)(blockIdx.x / S.n) * kWavesPerBlock + threadIdx.x / kWave;
-    double acc = 0.0;
 
     for (int64_t w0 = S.off[x_slice] + wave * RPW; w0 < s_end; w0 += nwaves * RPW) {
         const int nw = (int)min((int64_t)RPW, s_end - w0);
@@ -86,42 +85,16 @@ __global__ __launch_bounds__(kBlock) void k_read(ReadArgs<T> A, SliceTab S) {
             T pred = predict_one<T, KERN>(s, bu[x], bi[x], h);
             if (have[x] && l == 0) {
                 const int64_t j = w0 + x * R + g;
-                if constexpr (SSE) {
-                    const T err = A.r[j] - pred;             // :313
-                    acc += (double)err * (double)err;
-                } else {
-                    if (A.bound) {                           // :532-536
-                        if (pred > h.hi) pred = h.hi;
-                        else if (pred < h.lo) pred = h.lo;
-                    }
-                    A.out[j] = pred;
+                if (A.bound) {                               // :532-536
+                    if (pred > h.hi) pred = h.hi;
+                    else if (pred < h.lo) pred = h.lo;
                 }
+                A.out[j] = pred;
             }
-        }
-    }
-
-    if constexpr (SSE) {
-        // deterministic block reduction: wave butterfly, then 4 partials
-        acc = wave_sum(acc);
-        __shared__ double red[kWavesPerBlock];
-        if (lane == 0) red[threadIdx.x / kWave] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-#pragma unroll
-            for (int w = 0; w < kWavesPerBlock; ++w) t += red[w];
-            A.partials[blockIdx.x] = t;
         }
     }
 }
 
-// Training SSE, streaming form.  Each wave owns a contiguous run of its
-// slice; triples arrive 64 at a time in three coalesced loads (lane j holds
-// rating j of the chunk) and the NEXT chunk's triples are loaded before the
-// current chunk is consumed, so the only exposed latency is the row gather
-// (U groups of R ratings in flight).  In mf_sched_slices order consecutive
-// ratings share the user's P row (L1/L2 hits) and a slice's Q rows stay in
-// one XCD's L2.
 // Fixed-order sum of the per-block partials (one block).
 __global__ __launch_bounds__(kBlock) void k_sum_partials(const double* part, int n,
                                                          double* out) {
@@ -147,23 +120,23 @@ inline int read_bps(const SliceTab& S, int rpw) {
 }
 
 struct ReadLaunch {
-    const int32_t* u; const int32_t* i; const void* r; int64_t n;
+    const int32_t* u; const int32_t* i; int64_t n;
     double mu; const void* bu; const void* bi; const void* P; const void* Q;
     int32_t k; double gamma, lo, hi; int32_t bound; void* out;
-    double* partials; double* sse_out; hipStream_t stream; SliceTab S;
+    hipStream_t stream; SliceTab S;
 
     template <typename T, int GS, int V, int KERN>
     int run() {
         constexpr int RPW = Tile<T, V>::U * (kWave / GS);
         ReadArgs<T> a;
-        a.u = u; a.i = i; a.r = static_cast<const T*>(r);
+        a.u = u; a.i = i; a.r = nullptr;
         a.P = static_cast<const T*>(P); a.Q = static_cast<const T*>(Q);
         a.Bu = static_cast<const T*>(bu); a.Bi = static_cast<const T*>(bi);
         a.n = n; a.k = k; a.bound = bound; a.out = static_cast<T*>(out);
-        a.partials = partials;
+        a.partials = nullptr;
         a.h = make_hyper<T>(mu, 0.0, 0.0, gamma, lo, hi);
         const int blocks = read_bps(S, RPW) * S.n;
-        hipLaunchKernelGGL((k_read<T, GS, V, KERN, false>), dim3(blocks), dim3(kBlock), 0,
+        hipLaunchKernelGGL((k_read<T, GS, V, KERN>), dim3(blocks), dim3(kBlock), 0,
                            stream, a, S);
         MF_HIP_CHECK(hipGetLastError());
         return MF_OK;
@@ -238,7 +211,7 @@ extern "C" int mf_sgd_epoch(const int32_t* user_ids, const int32_t* item_ids,
                 global_mean, user_biases, item_biases, user_features, item_features,
                 n_factors, kernel, gamma, lr, reg, min_rating, max_rating,
                 update_user_params ? 1 : 0, update_item_params ? 1 : 0, flags,
-                (hipStream_t)stream, kernel_ms, claim, n_users};
+                (hipStream_t)stream, kernel_ms, claim};
     if (dtype == MF_F32) return sgd_launch_f32(P);
     if (dtype == MF_F64) return sgd_launch_f64(P);
     set_error("unknown dtype code %d", dtype);
@@ -860,9 +833,9 @@ extern "C" int mf_predict(const int32_t* user_ids, const int32_t* item_ids,
     if (n_pairs == 0) return MF_OK;
     SliceTab S;
     S.n = 1; S.off[0] = 0; S.off[1] = n_pairs;
-    ReadLaunch L{user_ids, item_ids, nullptr, n_pairs, global_mean, user_biases,
+    ReadLaunch L{user_ids, item_ids, n_pairs, global_mean, user_biases,
                  item_biases, user_features, item_features, n_factors, gamma,
-                 min_rating, max_rating, bound_ratings ? 1 : 0, out, nullptr,
-                 nullptr, (hipStream_t)stream, S};
+                 min_rating, max_rating, bound_ratings ? 1 : 0, out,
+                 (hipStream_t)stream, S};
     return dispatch(dtype, n_factors, kernel, L);
 }

@@ -191,19 +191,6 @@ def sched_tiles(u: np.ndarray, i: np.ndarray, n_users: int, n_items: int, n_chun
     return sched, offs
 
 
-# the training-RMSE pass's evaluation tiles (user chunks, item slices) per
-# dtype; env MF_SSE_TILES="C,S" overrides (probes: tools/sse_tiles_probe.py)
-EVAL_TILES = {"float32": (1, N_SLICES), "float64": (1, N_SLICES)}
-
-
-def eval_tiles(dtype: str) -> Tuple[int, int]:
-    env = os.environ.get("MF_SSE_TILES")
-    if env:
-        c, s_ = (int(x) for x in env.split(","))
-        return c, s_
-    return EVAL_TILES.get(dtype, (1, N_SLICES))
-
-
 # ------------------------------------------------ item-stationary RMSE pass
 # User super-windows per phase of the item-stationary pass (one launch each;
 # MF_SSE_SLAB_W overrides; tools/sse_slab_probe.py).
@@ -763,13 +750,7 @@ class SGDEngine:
         if sse_slab_selected(self.dtype, self.n, self.n_users, self.n_items, self.k) \
                 and self._build_eval_slab():
             return
-        n_chunks, n_slices = eval_tiles(self.dtype)
-        if os.environ.get("MF_EVAL_ORDER") == "host":
-            sched, offs = sched_tiles(self.u_host, self.i_host, self.n_users, self.n_items,
-                                      n_chunks, n_slices)
-            d_sched = torch.from_numpy(sched).to(self.dev).long()
-        else:
-            d_sched, offs = self._eval_order_device(n_chunks, n_slices)
+        d_sched, offs = self._eval_order_device(N_SLICES)
         # reorder on the device from the uploaded triples
         self.eu = self.u.index_select(0, d_sched)
         self.ei = self.i.index_select(0, d_sched)
@@ -816,35 +797,25 @@ class SGDEngine:
                       self.max_rating, _tp(sl["tab"]), sl["groups"], sl["windows"], sl["items"],
                       sl["stride"], _tp(ws), int(max_blocks), out, stream, attrs)
 
-    def _eval_order_device(self, n_chunks: int, n_slices: int):
-        """mf_sched_tiles' order computed on the GPU from the uploaded ids:
-        a stable sort of key = (user chunk * n_slices + item slice) * n_users
-        + user -- the host order exactly (tiles by a stable partition, users
-        ascending, ties in rating order), in ~tens of ms instead of the
-        host's ~0.4 s at C3 (fit()'s engine build)."""
+    def _eval_order_device(self, n_slices: int):
+        """mf_sched_slices' order computed on the GPU from the uploaded ids:
+        a stable sort of key = item slice * n_users + user -- the host order
+        exactly (slices by a stable partition, users ascending, ties in
+        rating order), in ~tens of ms instead of the host's ~0.4 s at C3
+        (fit()'s engine build)."""
         with torch.cuda.device(self.dev):
             u = self.u.long()
             i = self.i.long()
             n, nu = self.n, self.n_users
             sl = torch.div(i * n_slices, max(self.n_items, 1), rounding_mode="floor")
-            if n_chunks > 1:
-                deg = torch.bincount(u, minlength=nu)
-                before = torch.cumsum(deg, 0) - deg            # ratings of users < x
-                chunk_of = torch.clamp(torch.div(before * n_chunks, n, rounding_mode="floor"),
-                                       max=n_chunks - 1)
-                tile = chunk_of.index_select(0, u) * n_slices + sl
-                del deg, before, chunk_of
-            else:
-                tile = sl
-            key = tile * nu + u
-            del sl, i, tile
+            key = sl * nu + u
+            del sl, i
             skey, order = torch.sort(key, stable=True)
             del key, u
-            # tile t starts at the first key >= t * n_users (a search in the
+            # slice t starts at the first key >= t * n_users (a search in the
             # sorted keys: a histogram of 10^8 ids into 8 bins is ~4 ms of
             # atomics on one address each)
-            T = n_chunks * n_slices
-            edges = torch.arange(T + 1, dtype=torch.int64, device=skey.device) * nu
+            edges = torch.arange(n_slices + 1, dtype=torch.int64, device=skey.device) * nu
             offs = torch.searchsorted(skey, edges).cpu().numpy().astype(np.int64)
             offs[-1] = n
             return order, offs

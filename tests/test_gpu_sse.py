@@ -1,12 +1,10 @@
 """The training-RMSE pass (mf_sse, _calculate_rmse kernel_matrix_factorization.py:
-240-317) in its kernel variants: k_sse_lean (the default: biases loaded once
-per chunk), its round-5 form with a bias load per rating (variant 12),
-k_sse_owned (user rows owned per run; variant 6),
-k_sse_pipe (the same walk software-pipelined, pieces of 8 or 4 ratings) and
-k_sse_stream.  Per rating the arithmetic is identical; the FP64 sums differ
-only in accumulation order (the grid follows each kernel's occupancy), so
-they agree to 1e-12 relative, and with the FP64 oracle to 1e-9 relative
-(FP32 products and dot-product order)."""
+240-317) in its kernels: k_sse_lean (the default: user rows owned per run,
+biases loaded once per chunk) and k_sse_stream (the fallback for P or Q of
+4 GiB or more, reached here through MF_SSE_VARIANT=1).  Per rating the
+arithmetic is identical; the FP64 sums differ only in accumulation order (the
+grid follows each kernel's occupancy), so they agree to 1e-12 relative, and
+with the FP64 oracle to 1e-9 relative (FP32 products and dot-product order)."""
 import os
 
 import numpy as np
@@ -34,7 +32,7 @@ def test_sse_variants_agree(k, nu, ni, nnz, monkeypatch):
                     global_mean=float(r.mean()), min_rating=1, max_rating=5)
     eng.load_params(P, Q, bu, bi)
     got = {}
-    for slot, var in enumerate(("0", "4", "5", "1", "6", "12")):
+    for slot, var in enumerate(("0", "1")):
         monkeypatch.setenv("MF_SSE_VARIANT", var)
         eng.sse_async(slot)
         got[var] = eng.sse_values(slot + 1)[slot]
@@ -47,10 +45,11 @@ def test_sse_variants_agree(k, nu, ni, nnz, monkeypatch):
         assert abs(v - ref) <= 1e-9 * ref, (got, ref)
 
 
-@pytest.mark.parametrize("tiles", ["1,8", "4,16", "8,16", "2,32", "16,8"])
-def test_device_eval_order_equals_host(tiles, monkeypatch):
+@pytest.mark.parametrize("n_slices", [8, 16])
+def test_device_eval_order_equals_host(n_slices):
     """The evaluation order computed on the GPU (engine._eval_order_device:
-    stable sort by tile and user) is mf_sched_tiles' host order exactly."""
+    stable sort by item slice and user) is mf_sched_tiles' host order of one
+    user chunk exactly."""
     from matrix_factorization.engine import SGDEngine, sched_tiles
 
     rs = np.random.RandomState(11)
@@ -59,24 +58,24 @@ def test_device_eval_order_equals_host(tiles, monkeypatch):
     u = (keys // ni).astype(np.int32)
     i = (keys % ni).astype(np.int32)
     r = rs.randint(1, 6, nnz).astype(np.float64)
-    monkeypatch.setenv("MF_SSE_TILES", tiles)
     eng = SGDEngine(u, i, r, nu, ni, 16, "linear", "float64", "cuda:0")
-    c, s = (int(x) for x in tiles.split(","))
-    order, offs = eng._eval_order_device(c, s)
-    hs, ho = sched_tiles(u, i, nu, ni, c, s)
+    order, offs = eng._eval_order_device(n_slices)
+    hs, ho = sched_tiles(u, i, nu, ni, 1, n_slices)
     assert np.array_equal(order.cpu().numpy(), hs) and np.array_equal(offs, ho)
-    assert np.array_equal(eng.eu.cpu().numpy(), u[hs])
+    if n_slices == 8:                  # the engine's own evaluation copy
+        assert np.array_equal(eng.eu.cpu().numpy(), u[hs])
 
 
 @pytest.mark.parametrize("dtype,k", [("float64", 64), ("float32", 64), ("float64", 20)])
-@pytest.mark.parametrize("tiles", ["4,16", "1,16", "8,8"])
-def test_phased_tile_pass_agrees(dtype, k, tiles, monkeypatch):
-    """The FP64 pass over tiles walked in phases by a resident grid
-    (k_sse_phased) and the dispatch-ordered walk of the same tiles give the
-    default pass's SSE up to FP64 summation order (1e-12 relative) and the
-    oracle's to 1e-9."""
+@pytest.mark.parametrize("n_slices", [16, 24, 12])
+def test_many_slices_pass_agrees(dtype, k, n_slices):
+    """mf_sse over more than 8 slices (k_sse_lean; a multiple of 8 is dealt
+    part by part, slice_wave) gives the default 8-slice pass's SSE up to FP64
+    summation order (1e-12 relative), and the default the oracle's to 1e-9."""
+    import torch
+
     import oracle
-    from matrix_factorization.engine import SGDEngine
+    from matrix_factorization.engine import SGDEngine, sched_tiles
 
     rs = np.random.RandomState(k + 5)
     nu, ni, nnz = 20000, 4000, 600000
@@ -88,21 +87,22 @@ def test_phased_tile_pass_agrees(dtype, k, tiles, monkeypatch):
     Q = rs.normal(0, 0.3, (ni, k)).astype(dtype)
     bu = rs.normal(0, 0.1, nu).astype(dtype)
     bi = rs.normal(0, 0.1, ni).astype(dtype)
-    monkeypatch.delenv("MF_SSE_TILES", raising=False)
     eng = SGDEngine(u, i, r, nu, ni, k, "linear", dtype, "cuda:0",
                     global_mean=float(r.mean()), min_rating=1, max_rating=5)
     eng.load_params(P, Q, bu, bi)
+    assert eng.slab is None and len(eng.eval_offs) == 9
     eng.sse_async(0)
     base = eng.sse_values(1)[0]
-    monkeypatch.setenv("MF_SSE_TILES", tiles)
-    eng._build_eval()
-    got = []
-    for slot, ph in enumerate(("1", "0")):
-        monkeypatch.setenv("MF_SSE_PHASED", ph)
-        eng.sse_async(slot)
-        got.append(eng.sse_values(slot + 1)[slot])
-    for v in got:
-        assert abs(v - base) <= 1e-12 * base, (got, base)
+    # the engine's evaluation copy in the order of n_slices slices
+    sched, offs = sched_tiles(u, i, nu, ni, 1, n_slices)
+    d_sched = torch.from_numpy(sched).to(eng.u.device).long()
+    eng.eu = eng.u.index_select(0, d_sched)
+    eng.ei = eng.i.index_select(0, d_sched)
+    eng.er = eng.r.index_select(0, d_sched)
+    eng.eval_offs = offs
+    eng.sse_async(0)
+    got = eng.sse_values(1)[0]
+    assert abs(got - base) <= 1e-12 * base, (got, base)
     ref = oracle.sse(u, i, r.astype(np.float64), eng.global_mean, bu.astype(np.float64),
                      bi.astype(np.float64), P.astype(np.float64), Q.astype(np.float64))
     assert abs(base - ref) <= 1e-9 * ref

@@ -53,7 +53,7 @@ def _slab_env(monkeypatch, on, windows=None, lds=None):
         else:
             monkeypatch.setenv(name, str(v))
     for name in ("MF_SSE_SLAB_PAD", "MF_SSE_SLAB_WAVES", "MF_SSE_SLAB_SETS", "MF_SSE_BESIDE",
-                 "MF_SSE_TILES", "MF_SSE_VARIANT"):
+                 "MF_SSE_VARIANT"):
         monkeypatch.delenv(name, raising=False)
 
 

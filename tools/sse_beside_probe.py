@@ -102,71 +102,66 @@ def main():
     res["snapshot_ms"] = stats(t)
     log(f"snapshot {res['snapshot_ms']}")
 
-    for tiles in ("1,8", "1,1"):
-        os.environ["MF_SSE_TILES"] = tiles
-        eng._build_eval()
+    out = {}
+    # pass alone: full grid, live parameters
+    t = []
+    for _ in range(REPS):
+        a, b = E(), E()
+        a.record()
+        eng.sse_async(1)
+        b.record()
         torch.cuda.synchronize()
-        key = "tiles_" + tiles.replace(",", "x")
-        out = {}
-        # pass alone: full grid, live parameters
+        t.append(a.elapsed_time(b))
+    out["pass_full_ms"] = stats(t)
+    # pass alone: capped grid, snapshot
+    take_snapshot()
+    for cap in (cus, 2 * cus):
         t = []
         for _ in range(REPS):
             a, b = E(), E()
             a.record()
-            eng.sse_async(1)
+            eng.sse_from(2, *snap, ws2, main_s, max_blocks=cap)
             b.record()
             torch.cuda.synchronize()
             t.append(a.elapsed_time(b))
-        out["pass_full_ms"] = stats(t)
-        # pass alone: capped grid, snapshot
-        take_snapshot()
-        for cap in (cus, 2 * cus):
-            t = []
-            for _ in range(REPS):
-                a, b = E(), E()
-                a.record()
-                eng.sse_from(2, *snap, ws2, main_s, max_blocks=cap)
-                b.record()
-                torch.cuda.synchronize()
-                t.append(a.elapsed_time(b))
-            out[f"pass_capped{cap}_ms"] = stats(t)
-        torch.cuda.synchronize()
-        v_full, v_cap = eng.sse_buf[1].item(), eng.sse_buf[2].item()
-        # together: snapshot, sweep enqueued, host waits, capped pass on the side stream
-        for wait_ms in (2.0, 0.0):
-            tot, swp, pas, snp = [], [], [], []
-            for _ in range(REPS):
-                torch.cuda.synchronize()
-                e0, e1, e2, e3, s0, s1 = E(), E(), E(), E(), E(), E()
-                e0.record()
-                take_snapshot()
-                e1.record()
-                side.wait_event(e1)
-                sweep()
-                e2.record()
-                if wait_ms:
-                    t0 = time.perf_counter()
-                    while (time.perf_counter() - t0) * 1e3 < wait_ms:
-                        pass
-                s0.record(side)
-                eng.sse_from(3, *snap, ws2, side, max_blocks=cus)
-                s1.record(side)
-                main_s.wait_event(s1)
-                e3.record()
-                torch.cuda.synchronize()
-                tot.append(e0.elapsed_time(e3))
-                snp.append(e0.elapsed_time(e1))
-                swp.append(e1.elapsed_time(e2))
-                pas.append(s0.elapsed_time(s1))
-            out[f"together_wait{wait_ms:g}ms"] = {
-                "total_ms": stats(tot), "snapshot_ms": stats(snp), "sweep_ms": stats(swp),
-                "pass_ms": stats(pas)}
-        out["sse_full"] = v_full
-        out["sse_capped"] = v_cap
-        res[key] = out
-        log(f"{key}: {json.dumps(out)}")
-        if eng.strata_failed():
-            raise SystemExit("a sweep gave up waiting")
+        out[f"pass_capped{cap}_ms"] = stats(t)
+    torch.cuda.synchronize()
+    v_full, v_cap = eng.sse_buf[1].item(), eng.sse_buf[2].item()
+    # together: snapshot, sweep enqueued, host waits, capped pass on the side stream
+    for wait_ms in (2.0, 0.0):
+        tot, swp, pas, snp = [], [], [], []
+        for _ in range(REPS):
+            torch.cuda.synchronize()
+            e0, e1, e2, e3, s0, s1 = E(), E(), E(), E(), E(), E()
+            e0.record()
+            take_snapshot()
+            e1.record()
+            side.wait_event(e1)
+            sweep()
+            e2.record()
+            if wait_ms:
+                t0 = time.perf_counter()
+                while (time.perf_counter() - t0) * 1e3 < wait_ms:
+                    pass
+            s0.record(side)
+            eng.sse_from(3, *snap, ws2, side, max_blocks=cus)
+            s1.record(side)
+            main_s.wait_event(s1)
+            e3.record()
+            torch.cuda.synchronize()
+            tot.append(e0.elapsed_time(e3))
+            snp.append(e0.elapsed_time(e1))
+            swp.append(e1.elapsed_time(e2))
+            pas.append(s0.elapsed_time(s1))
+        out[f"together_wait{wait_ms:g}ms"] = {
+            "total_ms": stats(tot), "snapshot_ms": stats(snp), "sweep_ms": stats(swp),
+            "pass_ms": stats(pas)}
+    out["sse_full"] = v_full
+    out["sse_capped"] = v_cap
+    res["pass"] = out
+    log(f"pass: {json.dumps(out)}")
+    if eng.strata_failed():
+        raise SystemExit("a sweep gave up waiting")
     with open(ARGS.out, "w") as f:
         json.dump(res, f, indent=1)
     log("done")

@@ -44,13 +44,7 @@ def main():
     print(f"# {desc}: {nb} colours", file=sys.stderr, flush=True)
     X, NT, NQ = _lib.MF_FLAG_XCD_SWIZZLE, _lib.MF_FLAG_NT_USER, _lib.MF_FLAG_NT_ITEM
     CL = _lib.MF_FLAG_XCD_CLAIM
-    variants = {    # float4 layout, k=64: tile 0 -> S=4 slots (16 ratings/wave),
-                    # 1 -> S=2, 2 -> S=8, 3 -> S=1
-        "s4_nt": X | NT, "s4_nt_noxcd": NT, "s4": X,
-    }
-    # user-row cache policies (mf_rows.hpp kPolAux; flags bits 12..15)
-    for pol in range(2, 8):
-        variants[f"p{pol}"] = X | (pol << 12)
+    variants = {"s4_nt": X | NT, "s4_nt_noxcd": NT, "s4": X}
     if args.variants:
         variants = {kk: v for kk, v in variants.items() if kk in args.variants.split(",")}
     res = {kk: {"kernel_ms": [], "wall_ms": [], "wall_nt_ms": []} for kk in variants}
