@@ -854,6 +854,98 @@ int mf_cf_rank(const int32_t* query_ids, int32_t n_query, int32_t query_side,
                const int32_t* target_items, void* workspace, int32_t* out_rank,
                int32_t* out_candidates, void* stream);
 
+/*
+ * Stored neighbours: a top-M similarity in place of the dense matrix, for
+ * entity counts whose n_entities^2 floats do not fit.
+ *
+ * The model.  With n_stored = M, the neighbour set N_M(a) of entity a is the
+ * first min(M, n_entities - 1) entities b != a under the order of the
+ * n_neighbors cut: S[a,b] descending with -0 tied to +0, then b ascending; S
+ * is mf_cf_similarity's float32 value.  A prediction for target e and other o
+ * is mf_cf_predict's with one change: the candidates are the b != e of o's
+ * list with r_bo > 0 AND b in N_M(e).  An entity outside N_M(e) is no
+ * candidate (not "similarity 0").  Everything else -- the cut at n_neighbors,
+ * the FP64 sum and its order, m_e with no candidate or a zero denominator,
+ * global_mean for an unknown id, the clipping -- is unchanged.  N_M is per row
+ * and not symmetric: row e serves target e.  Hence: the stored similarities
+ * are the dense S[a,b] bit for bit, and with M >= n_entities - 1 every
+ * prediction, score, top-k and rank is the dense entry point's bit for bit.
+ *
+ * mf_cf_neighbours: builds the lists from the inputs of mf_cf_similarity.
+ *   entity_ptr .. pass_cols                as for mf_cf_similarity
+ *   n_stored        M, in [1, 4096]
+ *   workspace       DEVICE, mf_cf_neighbours_workspace_bytes(n_entities,
+ *                   n_stored) = 4 n_entities min(n_entities, 2048) bytes: one
+ *                   float32 scratch row for each of the (at most 2048)
+ *                   workgroups in flight -- it scales with the rows in
+ *                   flight, not with n_entities^2; free after the call's work
+ *   nbr_ids         DEVICE, int32, n_entities x n_stored row-major: row a
+ *                   holds N_M(a) sorted by id ascending, then -1 where
+ *                   n_entities - 1 < n_stored; EVERY element is written
+ *   nbr_sims        DEVICE, float, same shape: S[a, nbr_ids[a, j]], 0 in the
+ *                   padding; every element is written
+ * A persistent one-wave workgroup takes rows a = w, w + 2048, ...: the row's
+ * column ranges in sequence through mf_cf_similarity's accumulation and FP64
+ * epilogue (one code path: the same values bit for bit) into its scratch row,
+ * the M-th key by mf_cf_predict's exact radix select with the keys rebuilt
+ * from the scratch row, then one ordered pass that emits the columns at or
+ * above the cut, placed by a ballot prefix count.  A row of zero norm is all
+ * zeros: its set is the M lowest ids != a.  The dense row never exists in HBM
+ * outside the scratch row.  No floating-point atomics; the result depends
+ * neither on pass_cols nor on the grid.
+ *
+ * mf_cf_predict_nbr, mf_cf_scores_nbr, mf_cf_topk_nbr, mf_cf_rank_nbr: the
+ * four entry points above with (nbr_ids, nbr_sims, n_stored) -- mf_cf_neighbours'
+ * output -- in place of `similarity`; every other argument, output and limit
+ * as documented there.  The kernels are the same (a template parameter picks
+ * the accessor): candidate b of target e is looked up by binary search in e's
+ * id-ascending row, absent = not a candidate.  With MF_CF_QUERY_ENTITY the
+ * query's row (8 n_stored bytes, at most 32 KiB) is staged in LDS; with
+ * MF_CF_QUERY_OTHER the query's list is staged as before and each target's
+ * row is read through L2.
+ *
+ * All six: the checks of their dense counterparts, and n_stored in [1, 4096],
+ * no NULL for nbr_ids, nbr_sims (where `similarity` may not be NULL) or the
+ * workspace -- else MF_ERR_INVALID, before any device work, with the
+ * argument's name in mf_last_error().  Zero sizes return MF_OK.
+ */
+size_t mf_cf_neighbours_workspace_bytes(int32_t n_entities, int32_t n_stored);
+int mf_cf_neighbours(const int64_t* entity_ptr, const int32_t* other_ids, const void* ratings,
+                     const int64_t* other_ptr, const int32_t* entity_ids,
+                     const void* other_ratings, int32_t n_entities, int32_t n_others,
+                     int32_t dtype, const double* mean, const double* norm, int32_t pass_cols,
+                     int32_t n_stored, void* workspace, int32_t* nbr_ids, void* nbr_sims,
+                     void* stream);
+int mf_cf_predict_nbr(const int32_t* entity_ids, const int32_t* other_ids, int64_t n_pairs,
+                      const int64_t* other_ptr, const int32_t* list_entity_ids,
+                      const void* list_ratings, const int32_t* nbr_ids, const void* nbr_sims,
+                      int32_t n_stored, const double* mean, int32_t n_entities, int32_t n_others,
+                      int32_t dtype, int32_t n_neighbors, double global_mean, double min_rating,
+                      double max_rating, int32_t bound_ratings, double* out, void* stream);
+int mf_cf_scores_nbr(const int32_t* query_ids, int32_t n_query, int32_t query_side,
+                     const int64_t* other_ptr, const int32_t* list_entity_ids,
+                     const void* list_ratings, const int32_t* nbr_ids, const void* nbr_sims,
+                     int32_t n_stored, const double* mean, int32_t n_entities, int32_t n_others,
+                     int32_t dtype, int32_t n_neighbors, double global_mean,
+                     int32_t targets_per_block, double* out, void* stream);
+int mf_cf_topk_nbr(const int32_t* query_ids, int32_t n_query, int32_t query_side,
+                   const int64_t* other_ptr, const int32_t* list_entity_ids,
+                   const void* list_ratings, const int32_t* nbr_ids, const void* nbr_sims,
+                   int32_t n_stored, const double* mean, int32_t n_entities, int32_t n_others,
+                   int32_t dtype, int32_t n_neighbors, double global_mean,
+                   int32_t targets_per_block, const int64_t* exclude_ptr,
+                   const int32_t* exclude_items, int32_t amount, void* workspace,
+                   int32_t* out_items, double* out_scores, void* stream);
+int mf_cf_rank_nbr(const int32_t* query_ids, int32_t n_query, int32_t query_side,
+                   const int64_t* other_ptr, const int32_t* list_entity_ids,
+                   const void* list_ratings, const int32_t* nbr_ids, const void* nbr_sims,
+                   int32_t n_stored, const double* mean, int32_t n_entities, int32_t n_others,
+                   int32_t dtype, int32_t n_neighbors, double global_mean,
+                   int32_t targets_per_block, const int64_t* exclude_ptr,
+                   const int32_t* exclude_items, const int64_t* target_ptr,
+                   const int32_t* target_items, void* workspace, int32_t* out_rank,
+                   int32_t* out_candidates, void* stream);
+
 /* ---------------- BPR: Bayesian personalised ranking ---------------------- */
 
 /*

@@ -18,6 +18,11 @@
 // order their own LDS accesses and meet at no workgroup barrier.
 //   LDS = 4 x (8 KiB keys + 1 KiB bins) + 12 KiB list (or the row): 48 KiB,
 //   3 workgroups = 12 waves per CU.
+// With stored neighbours (Sim = ListSim, the *_nbr entry points) a target's
+// similarities are its id-ascending row of at most 4096 (id, sim): a binary
+// search per candidate.  MF_CF_QUERY_ENTITY stages the query's row in LDS
+// (8 B an entry: up to 32 KiB + the 36 KiB above, 2 workgroups per CU at the
+// longest); MF_CF_QUERY_OTHER reads each target's short row through L2.
 // k_cf_rank_count: integer only; a workgroup per query, a thread per target,
 // the row's keys passing through LDS in tiles of 256.
 // No floating-point atomics; no result depends on the blocking of the targets
@@ -35,18 +40,20 @@ constexpr int kAutoTargets = 64;             // targets per workgroup: 16 per wa
 constexpr int kRowLdsMax = 4096;             // entities whose S row fits 16 KiB of LDS
 constexpr size_t kListLds = kKeysLds * (sizeof(double) + sizeof(int32_t));
 
+template <typename Sim>
 struct ScoreArgs {
     const int32_t* query;
     const int64_t* optr; const int32_t* oent; const float* orr;
-    const float* S; const double* mean;
+    Sim sim; const double* mean;
     uint64_t* out;                               // [n_query x n_targets]: keys, or the doubles' bits
     int32_t n_query, side, n_entities, n_others, n_targets, n_neighbors, tpb, nblk, as_keys,
         row_lds, query_major;
     double global_mean;
 };
 
+template <typename Sim>
 __global__ void __launch_bounds__(kBlock)
-k_cf_scores(const ScoreArgs A) {
+k_cf_scores(const ScoreArgs<Sim> A) {
     __shared__ uint64_t keys[kWavesPerBlock][kKeysLds];
     __shared__ uint32_t bins[kWavesPerBlock][256];
     extern __shared__ double stage[];            // the query's list, or its S row
@@ -76,7 +83,6 @@ k_cf_scores(const ScoreArgs A) {
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
-    const size_t ne = (size_t)A.n_entities;
     if (A.side == MF_CF_QUERY_OTHER) {
         const int64_t beg = A.optr[qid], len = A.optr[qid + 1] - beg;
         const bool staged = len <= kKeysLds;
@@ -92,13 +98,13 @@ k_cf_scores(const ScoreArgs A) {
             }
         __syncthreads();
         for (int32_t e = t0 + wv; e < t1; e += kWavesPerBlock) {
-            const float* srow = A.S + (size_t)e * ne;
+            const auto srow = A.sim.row(e);
             const double me = A.mean[e];
             double pred;
             if (staged) {
                 auto build = [&](int64_t j) -> uint64_t {
                     const int32_t b = sid[j];
-                    return (b < 0 || b == e) ? 0 : make_key(srow[b], b);
+                    return (b < 0 || b == e) ? 0 : srow.key(b);
                 };
                 auto dev = [&](int64_t j, uint64_t) -> double { return sdev[j]; };
                 pred = pair_predict(keys[wv], bins[wv], len, A.n_neighbors, lane, me, build, dev,
@@ -109,7 +115,7 @@ k_cf_scores(const ScoreArgs A) {
                     if ((uint32_t)b >= (uint32_t)A.n_entities || b == e ||
                         !(A.orr[beg + j] > 0.f))
                         return 0;
-                    return make_key(srow[b], b);
+                    return srow.key(b);
                 };
                 auto dev = [&](int64_t j, uint64_t k) -> double {
                     return (double)A.orr[beg + j] - A.mean[key_id(k)];
@@ -121,11 +127,20 @@ k_cf_scores(const ScoreArgs A) {
         }
     } else {
         const int32_t e = qid;
-        const float* srow = A.S + (size_t)e * ne;
-        if (A.row_lds) {
+        auto srow = A.sim.row(e);
+        if constexpr (Sim::kLists) {                 // the query's stored row: sims, then ids
+            float* sims = reinterpret_cast<float*>(stage);
+            int32_t* ids = reinterpret_cast<int32_t*>(sims + srow.n);
+            for (int32_t c = tid; c < srow.n; c += kBlock) {
+                sims[c] = srow.sims[c];
+                ids[c] = srow.ids[c];
+            }
+            srow.sims = sims;
+            srow.ids = ids;
+        } else if (A.row_lds) {
             float* row = reinterpret_cast<float*>(stage);
-            for (int32_t c = tid; c < A.n_entities; c += kBlock) row[c] = srow[c];
-            srow = row;
+            for (int32_t c = tid; c < A.n_entities; c += kBlock) row[c] = srow.s[c];
+            srow.s = row;
         }
         __syncthreads();
         const double me = A.mean[e];
@@ -135,7 +150,7 @@ k_cf_scores(const ScoreArgs A) {
                 const int32_t b = A.oent[beg + j];
                 if ((uint32_t)b >= (uint32_t)A.n_entities || b == e || !(A.orr[beg + j] > 0.f))
                     return 0;
-                return make_key(srow[b], b);
+                return srow.key(b);
             };
             auto dev = [&](int64_t j, uint64_t k) -> double {
                 return (double)A.orr[beg + j] - A.mean[key_id(k)];
@@ -201,12 +216,16 @@ k_cf_rank_count(const uint64_t* __restrict__ keys, int32_t n_targets,
     }
 }
 
+
+// Dense: S.  Stored neighbours (n_stored >= 1): nbr_ids / nbr_sims.
 struct Model {
     const int64_t* optr; const int32_t* oent; const void* orr;
     const void* S; const double* mean;
     int32_t n_entities, n_others, dtype, n_neighbors;
     double global_mean;
     int32_t targets_per_block;
+    const int32_t* nbr_ids = nullptr; const void* nbr_sims = nullptr;
+    int32_t n_stored = 0;
 };
 
 inline int32_t targets_of(int32_t side, int32_t n_entities, int32_t n_others) {
@@ -220,7 +239,7 @@ inline bool row_in_lds(int32_t n_entities) {
 
 // the checks every entry point shares, up to the NULL pointers; *done: nothing to do
 static int check(const char* fn, const int32_t* query, int32_t n_query, int32_t side,
-                 const Model& M, bool* done) {
+                 const Model& M, bool lists, bool* done) {
     *done = false;
     if (M.dtype != MF_F32) {
         set_error("%s: dtype=%d (float32 only)", fn, M.dtype);
@@ -235,6 +254,7 @@ static int check(const char* fn, const int32_t* query, int32_t n_query, int32_t 
         set_error("%s: n_neighbors=%d (must be >= 1)", fn, M.n_neighbors);
         return MF_ERR_INVALID;
     }
+    if (lists && bad_n_stored(fn, M.n_stored)) return MF_ERR_INVALID;
     if (M.targets_per_block < 0) {
         set_error("%s: targets_per_block=%d (must be >= 0; 0 = automatic)", fn,
                   M.targets_per_block);
@@ -261,9 +281,12 @@ static int check(const char* fn, const int32_t* query, int32_t n_query, int32_t 
         return MF_ERR_INVALID;
     }
     if (M.n_entities > 0 && M.n_others > 0) {         // else every query is unknown or has no target
-        const void* need[] = {M.optr, M.S, M.mean};
-        const char* names[] = {"other_ptr", "similarity", "mean"};
-        if (null_arg(fn, need, names, 3)) return MF_ERR_INVALID;
+        const void* dense[] = {M.optr, M.S, M.mean};
+        const char* dense_names[] = {"other_ptr", "similarity", "mean"};
+        const void* stored[] = {M.optr, M.nbr_ids, M.nbr_sims, M.mean};
+        const char* stored_names[] = {"other_ptr", "nbr_ids", "nbr_sims", "mean"};
+        if (lists ? null_arg(fn, stored, stored_names, 4) : null_arg(fn, dense, dense_names, 3))
+            return MF_ERR_INVALID;
     }
     const int32_t nt = targets_of(side, M.n_entities, M.n_others);
     const int32_t tpb = mf_cf_targets_per_block(nt, M.targets_per_block);
@@ -276,27 +299,113 @@ static int check(const char* fn, const int32_t* query, int32_t n_query, int32_t 
     return MF_OK;
 }
 
-static void launch_scores(const int32_t* query, int32_t n_query, int32_t side, const Model& M,
-                          uint64_t* out, bool as_keys, hipStream_t stream) {
-    ScoreArgs a;
+template <typename Sim>
+static int launch_scores_as(const Sim& sim, const int32_t* query, int32_t n_query, int32_t side,
+                            const Model& M, uint64_t* out, bool as_keys, hipStream_t stream) {
+    ScoreArgs<Sim> a;
     a.query = query; a.n_query = n_query;
     a.optr = M.optr; a.oent = M.oent; a.orr = static_cast<const float*>(M.orr);
-    a.S = static_cast<const float*>(M.S); a.mean = M.mean; a.out = out;
+    a.sim = sim; a.mean = M.mean; a.out = out;
     a.side = side; a.n_entities = M.n_entities; a.n_others = M.n_others;
     a.n_targets = targets_of(side, M.n_entities, M.n_others);
-    if (a.n_targets == 0) return;
+    if (a.n_targets == 0) return MF_OK;
     a.n_neighbors = M.n_neighbors;
     a.tpb = mf_cf_targets_per_block(a.n_targets, M.targets_per_block);
     a.nblk = (a.n_targets + a.tpb - 1) / a.tpb;
     a.as_keys = as_keys ? 1 : 0;
-    a.row_lds = side == MF_CF_QUERY_ENTITY && row_in_lds(M.n_entities) ? 1 : 0;
+    a.row_lds = !Sim::kLists && side == MF_CF_QUERY_ENTITY && row_in_lds(M.n_entities) ? 1 : 0;
     a.global_mean = M.global_mean;
     const char* qm = std::getenv("MF_CF_QUERY_MAJOR");
     a.query_major = qm && *qm ? (std::atoi(qm) == 1 ? 1 : 0) : (side == MF_CF_QUERY_ENTITY ? 1 : 0);
     size_t lds = kListLds;
     if (side == MF_CF_QUERY_ENTITY) lds = a.row_lds ? sizeof(float) * (size_t)M.n_entities : 0;
-    hipLaunchKernelGGL(k_cf_scores, dim3((unsigned)((int64_t)n_query * a.nblk)), dim3(kBlock), lds,
+    auto kfn = k_cf_scores<Sim>;
+    if constexpr (Sim::kLists)
+        if (side == MF_CF_QUERY_ENTITY) {
+            // the query's stored row (<= 32 KiB) beside the 36 KiB of keys and bins
+            lds = (sizeof(float) + sizeof(int32_t)) * (size_t)sim.n_valid;
+            MF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)(kMaxStored * (sizeof(float) + sizeof(int32_t)))));
+        }
+    hipLaunchKernelGGL(kfn, dim3((unsigned)((int64_t)n_query * a.nblk)), dim3(kBlock), lds,
                        stream, a);
+    return MF_OK;
+}
+
+static int launch_scores(const int32_t* query, int32_t n_query, int32_t side, const Model& M,
+                         uint64_t* out, bool as_keys, hipStream_t stream) {
+    if (M.n_stored)
+        return launch_scores_as(list_sim(M.nbr_ids, M.nbr_sims, M.n_stored, M.n_entities), query,
+                                n_query, side, M, out, as_keys, stream);
+    return launch_scores_as(DenseSim{static_cast<const float*>(M.S), M.n_entities}, query,
+                            n_query, side, M, out, as_keys, stream);
+}
+
+// the three entry points, dense (mf_cf_*) and stored-neighbours (mf_cf_*_nbr) alike
+static int scores(const char* fn, bool lists, const int32_t* query_ids, int32_t n_query,
+                  int32_t query_side, const Model& M, double* out, void* stream) {
+    bool done;
+    if (int rc = check(fn, query_ids, n_query, query_side, M, lists, &done)) return rc;
+    if (done || targets_of(query_side, M.n_entities, M.n_others) == 0) return MF_OK;
+    if (!out) {
+        set_error("%s: out is NULL", fn);
+        return MF_ERR_INVALID;
+    }
+    if (int rc = launch_scores(query_ids, n_query, query_side, M, reinterpret_cast<uint64_t*>(out),
+                               false, (hipStream_t)stream))
+        return rc;
+    MF_HIP_CHECK(hipGetLastError());
+    return MF_OK;
+}
+
+static int topk(const char* fn, bool lists, const int32_t* query_ids, int32_t n_query,
+                int32_t query_side, const Model& M, const int64_t* exclude_ptr,
+                const int32_t* exclude_items, int32_t amount, void* workspace,
+                int32_t* out_items, double* out_scores, void* stream) {
+    if (amount < 1 || amount > 2048) {
+        set_error("%s: amount=%d (must be in [1, 2048])", fn, amount);
+        return MF_ERR_INVALID;
+    }
+    bool done;
+    if (int rc = check(fn, query_ids, n_query, query_side, M, lists, &done)) return rc;
+    if (done) return MF_OK;
+    const int32_t nt = targets_of(query_side, M.n_entities, M.n_others);
+    const void* need[] = {workspace, out_items, out_scores};
+    const char* names[] = {"workspace", "out_items", "out_scores"};
+    if (null_arg(fn, need, names, 3)) return MF_ERR_INVALID;
+    uint64_t* keys = static_cast<uint64_t*>(workspace);
+    if (int rc = launch_scores(query_ids, n_query, query_side, M, keys, true, (hipStream_t)stream))
+        return rc;
+    topk_select_f64(keys, n_query, nt, exclude_ptr, exclude_items, amount, out_items, out_scores,
+                    (hipStream_t)stream);
+    MF_HIP_CHECK(hipGetLastError());
+    return MF_OK;
+}
+
+static int rank(const char* fn, bool lists, const int32_t* query_ids, int32_t n_query,
+                int32_t query_side, const Model& M, const int64_t* exclude_ptr,
+                const int32_t* exclude_items, const int64_t* target_ptr,
+                const int32_t* target_items, void* workspace, int32_t* out_rank,
+                int32_t* out_candidates, void* stream) {
+    bool done;
+    if (int rc = check(fn, query_ids, n_query, query_side, M, lists, &done)) return rc;
+    if (done) return MF_OK;
+    const int32_t nt = targets_of(query_side, M.n_entities, M.n_others);
+    const void* need[] = {target_ptr, target_items, workspace, out_rank, out_candidates};
+    const char* names[] = {"target_ptr", "target_items", "workspace", "out_rank",
+                           "out_candidates"};
+    if (null_arg(fn, need, names, 5)) return MF_ERR_INVALID;
+    uint64_t* keys = static_cast<uint64_t*>(workspace);
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = launch_scores(query_ids, n_query, query_side, M, keys, true, s)) return rc;
+    if (nt > 0 && exclude_ptr && exclude_items)
+        topk_exclude_keys(keys, n_query, nt, exclude_ptr, exclude_items, s);
+    hipLaunchKernelGGL(k_cf_rank_count, dim3((unsigned)n_query), dim3(kBlock), 0, s,
+                       (const uint64_t*)keys, nt, target_ptr, target_items, out_rank,
+                       out_candidates);
+    MF_HIP_CHECK(hipGetLastError());
+    return MF_OK;
 }
 
 }  // namespace cf
@@ -327,17 +436,7 @@ extern "C" int mf_cf_scores(const int32_t* query_ids, int32_t n_query, int32_t q
                             double* out, void* stream) {
     const cf::Model M{other_ptr, list_entity_ids, list_ratings, similarity, mean, n_entities,
                       n_others, dtype, n_neighbors, global_mean, targets_per_block};
-    bool done;
-    if (int rc = cf::check("mf_cf_scores", query_ids, n_query, query_side, M, &done)) return rc;
-    if (done || cf::targets_of(query_side, n_entities, n_others) == 0) return MF_OK;
-    if (!out) {
-        set_error("mf_cf_scores: out is NULL");
-        return MF_ERR_INVALID;
-    }
-    cf::launch_scores(query_ids, n_query, query_side, M, reinterpret_cast<uint64_t*>(out), false,
-                      (hipStream_t)stream);
-    MF_HIP_CHECK(hipGetLastError());
-    return MF_OK;
+    return cf::scores("mf_cf_scores", false, query_ids, n_query, query_side, M, out, stream);
 }
 
 extern "C" int mf_cf_topk(const int32_t* query_ids, int32_t n_query, int32_t query_side,
@@ -350,23 +449,8 @@ extern "C" int mf_cf_topk(const int32_t* query_ids, int32_t n_query, int32_t que
                           double* out_scores, void* stream) {
     const cf::Model M{other_ptr, list_entity_ids, list_ratings, similarity, mean, n_entities,
                       n_others, dtype, n_neighbors, global_mean, targets_per_block};
-    if (amount < 1 || amount > 2048) {
-        set_error("mf_cf_topk: amount=%d (must be in [1, 2048])", amount);
-        return MF_ERR_INVALID;
-    }
-    bool done;
-    if (int rc = cf::check("mf_cf_topk", query_ids, n_query, query_side, M, &done)) return rc;
-    if (done) return MF_OK;
-    const int32_t nt = cf::targets_of(query_side, n_entities, n_others);
-    const void* need[] = {workspace, out_items, out_scores};
-    const char* names[] = {"workspace", "out_items", "out_scores"};
-    if (cf::null_arg("mf_cf_topk", need, names, 3)) return MF_ERR_INVALID;
-    uint64_t* keys = static_cast<uint64_t*>(workspace);
-    cf::launch_scores(query_ids, n_query, query_side, M, keys, true, (hipStream_t)stream);
-    topk_select_f64(keys, n_query, nt, exclude_ptr, exclude_items, amount, out_items, out_scores,
-                    (hipStream_t)stream);
-    MF_HIP_CHECK(hipGetLastError());
-    return MF_OK;
+    return cf::topk("mf_cf_topk", false, query_ids, n_query, query_side, M, exclude_ptr,
+                    exclude_items, amount, workspace, out_items, out_scores, stream);
 }
 
 extern "C" int mf_cf_rank(const int32_t* query_ids, int32_t n_query, int32_t query_side,
@@ -380,22 +464,55 @@ extern "C" int mf_cf_rank(const int32_t* query_ids, int32_t n_query, int32_t que
                           void* stream) {
     const cf::Model M{other_ptr, list_entity_ids, list_ratings, similarity, mean, n_entities,
                       n_others, dtype, n_neighbors, global_mean, targets_per_block};
-    bool done;
-    if (int rc = cf::check("mf_cf_rank", query_ids, n_query, query_side, M, &done)) return rc;
-    if (done) return MF_OK;
-    const int32_t nt = cf::targets_of(query_side, n_entities, n_others);
-    const void* need[] = {target_ptr, target_items, workspace, out_rank, out_candidates};
-    const char* names[] = {"target_ptr", "target_items", "workspace", "out_rank",
-                           "out_candidates"};
-    if (cf::null_arg("mf_cf_rank", need, names, 5)) return MF_ERR_INVALID;
-    uint64_t* keys = static_cast<uint64_t*>(workspace);
-    const hipStream_t s = (hipStream_t)stream;
-    cf::launch_scores(query_ids, n_query, query_side, M, keys, true, s);
-    if (nt > 0 && exclude_ptr && exclude_items)
-        topk_exclude_keys(keys, n_query, nt, exclude_ptr, exclude_items, s);
-    hipLaunchKernelGGL(cf::k_cf_rank_count, dim3((unsigned)n_query), dim3(kBlock), 0, s,
-                       (const uint64_t*)keys, nt, target_ptr, target_items, out_rank,
-                       out_candidates);
-    MF_HIP_CHECK(hipGetLastError());
-    return MF_OK;
+    return cf::rank("mf_cf_rank", false, query_ids, n_query, query_side, M, exclude_ptr,
+                    exclude_items, target_ptr, target_items, workspace, out_rank, out_candidates,
+                    stream);
+}
+
+// ---- the same three from stored neighbour lists (mf_cf_neighbours' output)
+extern "C" int mf_cf_scores_nbr(const int32_t* query_ids, int32_t n_query, int32_t query_side,
+                                const int64_t* other_ptr, const int32_t* list_entity_ids,
+                                const void* list_ratings, const int32_t* nbr_ids,
+                                const void* nbr_sims, int32_t n_stored, const double* mean,
+                                int32_t n_entities, int32_t n_others, int32_t dtype,
+                                int32_t n_neighbors, double global_mean,
+                                int32_t targets_per_block, double* out, void* stream) {
+    const cf::Model M{other_ptr, list_entity_ids, list_ratings, nullptr, mean, n_entities,
+                      n_others, dtype, n_neighbors, global_mean, targets_per_block,
+                      nbr_ids, nbr_sims, n_stored};
+    return cf::scores("mf_cf_scores_nbr", true, query_ids, n_query, query_side, M, out, stream);
+}
+
+extern "C" int mf_cf_topk_nbr(const int32_t* query_ids, int32_t n_query, int32_t query_side,
+                              const int64_t* other_ptr, const int32_t* list_entity_ids,
+                              const void* list_ratings, const int32_t* nbr_ids,
+                              const void* nbr_sims, int32_t n_stored, const double* mean,
+                              int32_t n_entities, int32_t n_others, int32_t dtype,
+                              int32_t n_neighbors, double global_mean, int32_t targets_per_block,
+                              const int64_t* exclude_ptr, const int32_t* exclude_items,
+                              int32_t amount, void* workspace, int32_t* out_items,
+                              double* out_scores, void* stream) {
+    const cf::Model M{other_ptr, list_entity_ids, list_ratings, nullptr, mean, n_entities,
+                      n_others, dtype, n_neighbors, global_mean, targets_per_block,
+                      nbr_ids, nbr_sims, n_stored};
+    return cf::topk("mf_cf_topk_nbr", true, query_ids, n_query, query_side, M, exclude_ptr,
+                    exclude_items, amount, workspace, out_items, out_scores, stream);
+}
+
+extern "C" int mf_cf_rank_nbr(const int32_t* query_ids, int32_t n_query, int32_t query_side,
+                              const int64_t* other_ptr, const int32_t* list_entity_ids,
+                              const void* list_ratings, const int32_t* nbr_ids,
+                              const void* nbr_sims, int32_t n_stored, const double* mean,
+                              int32_t n_entities, int32_t n_others, int32_t dtype,
+                              int32_t n_neighbors, double global_mean, int32_t targets_per_block,
+                              const int64_t* exclude_ptr, const int32_t* exclude_items,
+                              const int64_t* target_ptr, const int32_t* target_items,
+                              void* workspace, int32_t* out_rank, int32_t* out_candidates,
+                              void* stream) {
+    const cf::Model M{other_ptr, list_entity_ids, list_ratings, nullptr, mean, n_entities,
+                      n_others, dtype, n_neighbors, global_mean, targets_per_block,
+                      nbr_ids, nbr_sims, n_stored};
+    return cf::rank("mf_cf_rank_nbr", true, query_ids, n_query, query_side, M, exclude_ptr,
+                    exclude_items, target_ptr, target_items, workspace, out_rank, out_candidates,
+                    stream);
 }

@@ -15,7 +15,10 @@ exact-order SGD on sampled (user, positive, negative) triples.  ItemItemCF and
 UserUserCF are the reference's neighbourhood models
 (collaborative_filtering.py): a float32 similarity matrix built on the GPU
 from the sparse ratings (mf_cf_stats, mf_cf_similarity) and a
-top-n_neighbors weighted prediction (mf_cf_predict).  The content-based model
+top-n_neighbors weighted prediction (mf_cf_predict); with
+``stored_neighbors=M`` each entity's M best neighbours in place of the matrix
+(mf_cf_neighbours, mf_cf_*_nbr), for entity counts whose matrix does not fit.
+The content-based model
 of the reference is outside this build's scope.
 """
 

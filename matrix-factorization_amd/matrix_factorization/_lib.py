@@ -156,6 +156,23 @@ SIGNATURES = {
     "mf_cf_rank": (ctypes.c_int, [
         _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F64, _I32,
         _P, _P, _P, _P, _P, _P, _P, _P]),             # exclusions, targets, ws, rank, cand, stream
+    # stored neighbours (top-M): (nbr_ids, nbr_sims, n_stored) in place of the similarity
+    "mf_cf_neighbours_workspace_bytes": (ctypes.c_size_t, [_I32, _I32]),
+    "mf_cf_neighbours": (ctypes.c_int, [
+        _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32,     # as mf_cf_similarity ...
+        _I32, _P, _P, _P, _P]),                       # n_stored, ws, nbr_ids, nbr_sims, stream
+    "mf_cf_predict_nbr": (ctypes.c_int, [
+        _P, _P, _I64, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32,
+        _F64, _F64, _F64, _I32, _P, _P]),
+    "mf_cf_scores_nbr": (ctypes.c_int, [
+        _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32,
+        _F64, _I32, _P, _P]),
+    "mf_cf_topk_nbr": (ctypes.c_int, [
+        _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _F64, _I32,
+        _P, _P, _I32, _P, _P, _P, _P]),
+    "mf_cf_rank_nbr": (ctypes.c_int, [
+        _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _F64, _I32,
+        _P, _P, _P, _P, _P, _P, _P, _P]),
     "mf_bpr_max_factors": (ctypes.c_int32, []),
     "mf_bpr_sample": (ctypes.c_int, [
         _P, _P, _P, _I64, _P, _P, _I32, _I32,         # order, positives, n, CSR, n_users n_items

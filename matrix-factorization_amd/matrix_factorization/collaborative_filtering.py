@@ -27,6 +27,18 @@ item for a user in one pass that keeps what the user's pairs share on the chip
 (mf_cf_topk, mf_cf_rank): the same predictions bit for bit, ordered by score
 descending and internal item id ascending.
 
+``stored_neighbors=M`` (default None: the dense matrix) keeps only each
+entity's M best neighbours -- the first min(M, n - 1) entities b != a under
+(S[a,b] descending, b ascending), the order of the ``n_neighbors`` cut -- as
+n x M ids and float32 similarities (mf_cf_neighbours; 8 M bytes per entity,
+the dense row never exists in HBM), so the models fit where the n x n matrix
+does not.  A prediction for target e then takes its candidates only from e's
+stored row: an entity outside it is no candidate (not "similarity 0");
+everything else is unchanged, and with M >= n - 1 every prediction, score,
+top-k and rank is the dense model's bit for bit.  ``similarity_neighbors``
+returns the stored (ids, sims); the ``*_similarity_matrix`` attributes then
+raise rather than densify.
+
 Three deliberate departures from the reference:
 
 1. Ratings stay aligned to their pairs.  The reference's ``fit`` shuffles X in
@@ -49,7 +61,8 @@ import numpy as np
 import pandas as pd
 
 from . import _lib
-from .neighbours import DEFAULT_MAX_SIMILARITY_BYTES, NeighbourEngine, check_similarity_bytes
+from .neighbours import (DEFAULT_MAX_SIMILARITY_BYTES, MAX_STORED_NEIGHBORS, NeighbourEngine,
+                         check_neighbour_bytes, check_similarity_bytes)
 from .ranking import RankingMixin
 from .recommender_base import RecommenderBase
 
@@ -97,12 +110,27 @@ class _NeighbourhoodCF(RankingMixin, RecommenderBase):
 
     def __init__(self, min_rating: float = 0, max_rating: float = 5, n_neighbors: int = 50,
                  similarity_metric: str = "cosine", verbose: int = 0, device=None,
-                 max_similarity_bytes: int = DEFAULT_MAX_SIMILARITY_BYTES):
+                 max_similarity_bytes: int = DEFAULT_MAX_SIMILARITY_BYTES,
+                 stored_neighbors=None):
         super().__init__(min_rating=min_rating, max_rating=max_rating, verbose=verbose)
         self.n_neighbors = n_neighbors
         self.similarity_metric = similarity_metric
         self.device = device
         self.max_similarity_bytes = max_similarity_bytes
+        self.stored_neighbors = stored_neighbors
+
+    # stored_neighbors=None is the dense model unchanged in every respect, its
+    # parameter dict included: the parameter is listed once it is set
+    def get_params(self, deep: bool = True) -> dict:
+        params = super().get_params(deep=deep)
+        if params.get("stored_neighbors") is None:
+            params.pop("stored_neighbors", None)
+        return params
+
+    def set_params(self, **params):
+        if "stored_neighbors" in params:
+            self.stored_neighbors = params.pop("stored_neighbors")
+        return super().set_params(**params)
 
     # ------------------------------------------------------------ state
     def _sides(self):
@@ -120,7 +148,8 @@ class _NeighbourhoodCF(RankingMixin, RecommenderBase):
                 raise AttributeError(f"{type(self).__name__} is not fitted")
             ent, oth, n_ent, n_oth = self._sides()
             eng = NeighbourEngine(ent, oth, self._train_ratings, n_ent, n_oth, self.device,
-                                  int(self.max_similarity_bytes), what=self._ENTITY + "s")
+                                  int(self.max_similarity_bytes), what=self._ENTITY + "s",
+                                  stored_neighbors=self.stored_neighbors)
             self._engine = eng
         return eng
 
@@ -135,7 +164,8 @@ class _NeighbourhoodCF(RankingMixin, RecommenderBase):
 
     def __setstate__(self, state):
         for key, default in (("device", None),
-                             ("max_similarity_bytes", DEFAULT_MAX_SIMILARITY_BYTES)):
+                             ("max_similarity_bytes", DEFAULT_MAX_SIMILARITY_BYTES),
+                             ("stored_neighbors", None)):
             state.setdefault(key, default)
         self.__dict__.update(state)
         _warn_if_no_device(type(self).__name__)
@@ -156,6 +186,11 @@ class _NeighbourhoodCF(RankingMixin, RecommenderBase):
         if (isinstance(self.n_neighbors, bool) or not isinstance(self.n_neighbors, (int, np.integer))
                 or self.n_neighbors < 1):
             raise ValueError(f"n_neighbors must be an integer >= 1, got {self.n_neighbors!r}")
+        M = self.stored_neighbors
+        if M is not None and (isinstance(M, bool) or not isinstance(M, (int, np.integer))
+                              or not 1 <= M <= MAX_STORED_NEIGHBORS):
+            raise ValueError(f"stored_neighbors must be None or an integer in "
+                             f"[1, {MAX_STORED_NEIGHBORS}], got {M!r}")
         X = self._preprocess_data(X=X, y=y, type="fit")
         self.global_mean = X["rating"].mean()
         if self.similarity_metric not in METRICS:
@@ -165,7 +200,11 @@ class _NeighbourhoodCF(RankingMixin, RecommenderBase):
         self._train_items = X["item_id"].to_numpy(np.int32)
         self._train_ratings = X["rating"].to_numpy(np.float64)
         n_ent = self._sides()[2]
-        check_similarity_bytes(n_ent, int(self.max_similarity_bytes), self._ENTITY + "s")
+        if M is None:
+            check_similarity_bytes(n_ent, int(self.max_similarity_bytes), self._ENTITY + "s")
+        else:
+            check_neighbour_bytes(n_ent, int(M), int(self.max_similarity_bytes),
+                                  self._ENTITY + "s")
         eng = self._fitted_engine()
         self._means = eng.mean.cpu().numpy()
         return self
@@ -192,8 +231,26 @@ class _NeighbourhoodCF(RankingMixin, RecommenderBase):
     def _similarity_matrix(self):
         if self.__dict__.get("_train_users") is None:
             return None
+        if self.stored_neighbors is not None:
+            raise AttributeError(
+                f"{type(self).__name__}(stored_neighbors={self.stored_neighbors!r}) keeps no "
+                f"dense {self._ENTITY}_similarity_matrix; use similarity_neighbors")
         eng = self._fitted_engine()
         return eng.S.cpu().numpy()
+
+    @property
+    def similarity_neighbors(self):
+        """(ids int32, sims float32), each n_entities x stored_neighbors, as
+        stored: internal ids, every row id-ascending, padded with -1 / 0; None
+        before ``fit``.  A dense model (stored_neighbors=None) has none."""
+        if self.stored_neighbors is None:
+            raise AttributeError(
+                f"{type(self).__name__} with stored_neighbors=None keeps the dense matrix; use "
+                f"{self._ENTITY}_similarity_matrix")
+        if self.__dict__.get("_train_users") is None:
+            return None
+        eng = self._fitted_engine()
+        return eng.nbr_ids.cpu().numpy(), eng.nbr_sims.cpu().numpy()
 
     @property
     def user_item_matrix(self):
@@ -217,11 +274,16 @@ class ItemItemCF(_NeighbourhoodCF):
     computation, as in the reference), verbose=0; plus device and
     max_similarity_bytes (default 16 GiB: ``fit`` refuses, with a ValueError
     naming the size and before allocating anything, an n_items x n_items
-    float32 similarity larger than this).
+    float32 similarity larger than this) and stored_neighbors (default None:
+    the dense matrix; an integer M in [1, 4096] keeps each item's M best
+    neighbours instead -- module docstring -- and the budget then covers the
+    8 M n_items bytes of the lists plus the workspace that builds them).
 
     Attributes after fit: item_mean_ratings (float64 Series by internal item
     id), item_similarity_matrix (float32 ndarray fetched from the device on
-    access), user_item_matrix (dense frame, built on the host when read).
+    access; AttributeError with stored_neighbors), similarity_neighbors (the
+    stored (ids, sims); AttributeError without), user_item_matrix (dense frame,
+    built on the host when read).
 
     Departures from the reference (module docstring): ratings stay aligned to
     their pairs; the target item is never its own neighbour; ties at the
@@ -232,10 +294,12 @@ class ItemItemCF(_NeighbourhoodCF):
 
     def __init__(self, min_rating: float = 0, max_rating: float = 5, n_neighbors: int = 50,
                  similarity_metric: str = "cosine", verbose: int = 0, device=None,
-                 max_similarity_bytes: int = DEFAULT_MAX_SIMILARITY_BYTES):
+                 max_similarity_bytes: int = DEFAULT_MAX_SIMILARITY_BYTES,
+                 stored_neighbors=None):
         super().__init__(min_rating=min_rating, max_rating=max_rating, n_neighbors=n_neighbors,
                          similarity_metric=similarity_metric, verbose=verbose, device=device,
-                         max_similarity_bytes=max_similarity_bytes)
+                         max_similarity_bytes=max_similarity_bytes,
+                         stored_neighbors=stored_neighbors)
 
     @property
     def item_mean_ratings(self):
@@ -256,11 +320,16 @@ class UserUserCF(_NeighbourhoodCF):
     computation, as in the reference), verbose=0; plus device and
     max_similarity_bytes (default 16 GiB: ``fit`` refuses, with a ValueError
     naming the size and before allocating anything, an n_users x n_users
-    float32 similarity larger than this).
+    float32 similarity larger than this) and stored_neighbors (default None:
+    the dense matrix; an integer M in [1, 4096] keeps each user's M best
+    neighbours instead -- module docstring -- and the budget then covers the
+    8 M n_users bytes of the lists plus the workspace that builds them).
 
     Attributes after fit: user_mean_ratings (float64 Series by internal user
     id), user_similarity_matrix (float32 ndarray fetched from the device on
-    access), user_item_matrix (dense frame, built on the host when read).
+    access; AttributeError with stored_neighbors), similarity_neighbors (the
+    stored (ids, sims); AttributeError without), user_item_matrix (dense frame,
+    built on the host when read).
 
     Departures from the reference (module docstring): ratings stay aligned to
     their pairs; the target user is never their own neighbour; ties at the
@@ -271,10 +340,12 @@ class UserUserCF(_NeighbourhoodCF):
 
     def __init__(self, min_rating: float = 0, max_rating: float = 5, n_neighbors: int = 50,
                  similarity_metric: str = "cosine", verbose: int = 0, device=None,
-                 max_similarity_bytes: int = DEFAULT_MAX_SIMILARITY_BYTES):
+                 max_similarity_bytes: int = DEFAULT_MAX_SIMILARITY_BYTES,
+                 stored_neighbors=None):
         super().__init__(min_rating=min_rating, max_rating=max_rating, n_neighbors=n_neighbors,
                          similarity_metric=similarity_metric, verbose=verbose, device=device,
-                         max_similarity_bytes=max_similarity_bytes)
+                         max_similarity_bytes=max_similarity_bytes,
+                         stored_neighbors=stored_neighbors)
 
     @property
     def user_mean_ratings(self):

@@ -11,6 +11,13 @@ scores() / topk() / rank() take every target for a batch of queries in one
 pass (mf_cf_scores, mf_cf_topk, mf_cf_rank): the same predictions bit for bit,
 the queries in chunks that keep the key workspace within ``topk_ws_budget``.
 Ratings are float32 on the device; means, norms and predictions are FP64.
+
+``stored_neighbors=M`` keeps, in place of the dense n_entities x n_entities
+matrix, each entity's M best neighbours (mf_cf_neighbours: ids and float32
+similarities, id-ascending rows, 8 M bytes per entity; the dense row never
+exists in HBM) and routes predict / scores / topk / rank to the list variants
+(mf_cf_*_nbr): a candidate b counts for target e only when b is in e's stored
+row.  With M >= n_entities - 1 every result is the dense model's, bit for bit.
 """
 
 from __future__ import annotations
@@ -40,18 +47,49 @@ def check_similarity_bytes(n_entities: int, max_bytes: int, what: str = "entitie
             f"{max_bytes}")
 
 
+MAX_STORED_NEIGHBORS = 4096                  # a stored row is at most 32 KiB (mf_cf_neighbours)
+
+
+def neighbour_bytes(n_entities: int, stored_neighbors: int) -> tuple:
+    """(bytes of the stored lists, bytes of mf_cf_neighbours' workspace)."""
+    ws = int(_lib.load().mf_cf_neighbours_workspace_bytes(int(n_entities), int(stored_neighbors)))
+    return 8 * int(n_entities) * int(stored_neighbors), ws
+
+
+def check_neighbour_bytes(n_entities: int, stored_neighbors: int, max_bytes: int,
+                          what: str = "entities") -> None:
+    """Refuse, before anything is allocated, stored neighbour lists that, with
+    the workspace that builds them, are larger than ``max_bytes``."""
+    lists, ws = neighbour_bytes(n_entities, stored_neighbors)
+    if lists + ws > max_bytes:
+        raise ValueError(
+            f"the {stored_neighbors} stored neighbours of each of {n_entities} {what} need "
+            f"{lists} bytes and {ws} bytes of workspace to build, {lists + ws} bytes "
+            f"({(lists + ws) / 2**30:.2f} GiB), more than max_similarity_bytes={max_bytes}")
+
+
 class NeighbourEngine:
     """CSR lists, statistics and similarity of one fitted neighbourhood model.
 
     ent, oth, r: the training triples (internal ids, one rating per pair).
     Attributes: mean, norm (float64 device tensors, n_entities), S (float32
-    device tensor, n_entities x n_entities)."""
+    device tensor, n_entities x n_entities).  With ``stored_neighbors=M`` S is
+    None and nbr_ids (int32) / nbr_sims (float32), n_entities x M device
+    tensors, hold each entity's M best neighbours by id ascending (-1 / 0
+    padding)."""
 
     def __init__(self, ent: np.ndarray, oth: np.ndarray, r: np.ndarray, n_entities: int,
                  n_others: int, device=None,
                  max_similarity_bytes: int = DEFAULT_MAX_SIMILARITY_BYTES,
-                 pass_cols: int = 0, what: str = "entities"):
-        check_similarity_bytes(n_entities, max_similarity_bytes, what)
+                 pass_cols: int = 0, what: str = "entities", stored_neighbors=None):
+        self.stored = None if stored_neighbors is None else int(stored_neighbors)
+        if self.stored is None:
+            check_similarity_bytes(n_entities, max_similarity_bytes, what)
+        else:
+            if not 1 <= self.stored <= MAX_STORED_NEIGHBORS:
+                raise ValueError(f"stored_neighbors must be in [1, {MAX_STORED_NEIGHBORS}] or "
+                                 f"None, got {stored_neighbors!r}")
+            check_neighbour_bytes(n_entities, self.stored, max_similarity_bytes, what)
         ent = np.asarray(ent, dtype=np.int64)
         oth = np.asarray(oth, dtype=np.int64)
         if len(ent) and (ent.min() < 0 or ent.max() >= n_entities
@@ -67,15 +105,36 @@ class NeighbourEngine:
             self.other_csr = self._csr(d_oth, d_ent, d_r, self.n_others, self.n_entities)
             self.mean = torch.empty(self.n_entities, dtype=torch.float64, device=self.dev)
             self.norm = torch.empty(self.n_entities, dtype=torch.float64, device=self.dev)
-            self.S = torch.empty((self.n_entities, self.n_entities), dtype=torch.float32,
-                                 device=self.dev)
             eptr, eoth, er = self.entity_csr
             optr, oent, orr = self.other_csr
             _lib.call("mf_cf_stats", _tp(eptr), _tp(er), self.n_entities, self.n_others,
                       _lib.MF_F32, _tp(self.mean), _tp(self.norm), self.stream)
-            _lib.call("mf_cf_similarity", _tp(eptr), _tp(eoth), _tp(er), _tp(optr), _tp(oent),
-                      _tp(orr), self.n_entities, self.n_others, _lib.MF_F32, _tp(self.mean),
-                      _tp(self.norm), int(pass_cols), _tp(self.S), self.stream)
+            lists = (_tp(eptr), _tp(eoth), _tp(er), _tp(optr), _tp(oent), _tp(orr),
+                     self.n_entities, self.n_others, _lib.MF_F32, _tp(self.mean), _tp(self.norm),
+                     int(pass_cols))
+            self.S = self.nbr_ids = self.nbr_sims = None
+            if self.stored is None:
+                self.S = torch.empty((self.n_entities, self.n_entities), dtype=torch.float32,
+                                     device=self.dev)
+                _lib.call("mf_cf_similarity", *lists, _tp(self.S), self.stream)
+            else:
+                shape = (self.n_entities, self.stored)
+                self.nbr_ids = torch.empty(shape, dtype=torch.int32, device=self.dev)
+                self.nbr_sims = torch.empty(shape, dtype=torch.float32, device=self.dev)
+                ws = torch.empty(max(neighbour_bytes(self.n_entities, self.stored)[1], 4),
+                                 dtype=torch.uint8, device=self.dev)
+                _lib.call("mf_cf_neighbours", *lists, self.stored, _tp(ws), _tp(self.nbr_ids),
+                          _tp(self.nbr_sims), self.stream)
+                self.synchronize()                    # the workspace is freed here
+
+    def _fn(self, name: str) -> str:
+        return name if self.stored is None else name + "_nbr"
+
+    def _sim_args(self) -> tuple:
+        """The similarity operand of the prediction entry points."""
+        if self.stored is None:
+            return (_tp(self.S),)
+        return _tp(self.nbr_ids), _tp(self.nbr_sims), self.stored
 
     @property
     def stream(self):
@@ -105,9 +164,9 @@ class NeighbourEngine:
             d_o = torch.from_numpy(np.ascontiguousarray(oth, dtype=np.int32)).to(self.dev)
             for c0 in range(0, n, PREDICT_CHUNK):
                 m = min(PREDICT_CHUNK, n - c0)
-                _lib.call("mf_cf_predict", _VOID(d_e.data_ptr() + 4 * c0),
+                _lib.call(self._fn("mf_cf_predict"), _VOID(d_e.data_ptr() + 4 * c0),
                           _VOID(d_o.data_ptr() + 4 * c0), m, _tp(optr), _tp(oent), _tp(orr),
-                          _tp(self.S), _tp(self.mean), self.n_entities, self.n_others,
+                          *self._sim_args(), _tp(self.mean), self.n_entities, self.n_others,
                           _lib.MF_F32, int(n_neighbors), float(global_mean), float(min_rating),
                           float(max_rating), int(bool(bound)), _VOID(out.data_ptr() + 8 * c0),
                           self.stream)
@@ -135,7 +194,7 @@ class NeighbourEngine:
 
     def _model_args(self, n_neighbors: int, global_mean: float) -> tuple:
         optr, oent, orr = self.other_csr
-        return (_tp(optr), _tp(oent), _tp(orr), _tp(self.S), _tp(self.mean), self.n_entities,
+        return (_tp(optr), _tp(oent), _tp(orr), *self._sim_args(), _tp(self.mean), self.n_entities,
                 self.n_others, _lib.MF_F32, int(n_neighbors), float(global_mean),
                 int(self.targets_per_block))
 
@@ -168,7 +227,7 @@ class NeighbourEngine:
                 d_q = self._to(queries, np.int32)
                 for q0 in range(0, nq, chunk):
                     m = min(chunk, nq - q0)
-                    _lib.call("mf_cf_scores", _VOID(d_q.data_ptr() + 4 * q0), m, int(side),
+                    _lib.call(self._fn("mf_cf_scores"), _VOID(d_q.data_ptr() + 4 * q0), m, int(side),
                               *self._model_args(n_neighbors, global_mean),
                               _VOID(out.data_ptr() + 8 * nt * q0), self.stream)
         return out.cpu().numpy()
@@ -194,7 +253,7 @@ class NeighbourEngine:
                 m = min(chunk, nq - q0)
                 # CSR offsets stay absolute: the chunk's ptr array starts at row q0
                 dp = None if d_ptr is None else _VOID(d_ptr.data_ptr() + 8 * q0)
-                _lib.call("mf_cf_topk", _VOID(d_q.data_ptr() + 4 * q0), m, int(side),
+                _lib.call(self._fn("mf_cf_topk"), _VOID(d_q.data_ptr() + 4 * q0), m, int(side),
                           *self._model_args(n_neighbors, global_mean), dp, _tp(d_ex), amount,
                           _tp(ws), _VOID(items.data_ptr() + 4 * amount * q0),
                           _VOID(scores.data_ptr() + 8 * amount * q0), self.stream)
@@ -231,7 +290,7 @@ class NeighbourEngine:
                 m = min(chunk, nq - q0)
                 # both CSRs keep absolute offsets: their ptr arrays start at row q0
                 dp = None if d_ptr is None else _VOID(d_ptr.data_ptr() + 8 * q0)
-                _lib.call("mf_cf_rank", _VOID(d_q.data_ptr() + 4 * q0), m, int(side),
+                _lib.call(self._fn("mf_cf_rank"), _VOID(d_q.data_ptr() + 4 * q0), m, int(side),
                           *self._model_args(n_neighbors, global_mean), dp, _tp(d_ex),
                           _VOID(d_tp.data_ptr() + 8 * q0), _tp(d_ti), _tp(ws), _tp(ranks),
                           _VOID(cands.data_ptr() + 4 * q0), self.stream)
