@@ -575,8 +575,14 @@ __global__ __launch_bounds__(kBlock) void k_sse_stream(ReadArgs<T> A, SliceTab S
     }
 }
 
-// Training SSE with user rows OWNED by lane groups (same result as
-// k_sse_stream up to the order of the FP64 accumulation).  The wave's share
+// Training SSE with user rows OWNED by lane groups.  Against k_sse_stream
+// the FP64 accumulation runs in another order, and where a lane holds
+// several vectors of several values (W > 1 and V > 1) so does the lane's part
+// of the dot product: here each vector is summed on its own and the vector
+// sums are added, there all V W products are added in one chain.  The
+// ratings' errors then differ in their last bits (FP32 rank 100: RMSE by
+// 1e-10; tests/test_gpu_row_layouts.py); with W = 1 or V = 1 they are the
+// same bits.  The wave's share
 // of its slice is cut into R contiguous runs, one per group of GS lanes; in
 // mf_sched_slices order a run is user-major (a user has ~nnz/(n_users *
 // slices) consecutive ratings in a slice), so a group loads a user's P row
