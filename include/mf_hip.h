@@ -946,6 +946,53 @@ int mf_cf_rank_nbr(const int32_t* query_ids, int32_t n_query, int32_t query_side
                    const int32_t* target_items, void* workspace, int32_t* out_rank,
                    int32_t* out_candidates, void* stream);
 
+/* ---------------- Content-based ------------------------------------------- */
+
+/*
+ * ContentBasedRecommender (content_based.py).  F is the n_items x d FP64
+ * matrix of item feature rows (row-major, a zero row for an item without
+ * features), has_features[i] != 0 where item i has a row.  d is in
+ * [0, mf_max_factors()] everywhere.  All three entry points validate dtype,
+ * counts and d before any device work (MF_ERR_INVALID, the argument's name in
+ * mf_last_error()); a zero count returns MF_OK without touching the device.
+ *
+ * mf_content_profiles: one profile row per user,
+ *     P_u = sum_p w_p F_{i_p} / sum_p w_p     when sum_p w_p > 0,
+ *           sum_p w_p F_{i_p}                 otherwise (content_based.py:131),
+ * over the pairs p of the user's list whose item has features, in list order;
+ * a user without such a pair gets zeros.  FP64 throughout, no atomics: the
+ * same inputs give the same bits.
+ *   user_ptr        DEVICE, int64[n_users + 1]: CSR offsets of the lists
+ *   item_ids        DEVICE, int32: item of each pair (outside [0, n_items): skipped)
+ *   weights         DEVICE, double: w of each pair (rating - min_rating)
+ *   features        DEVICE, double[n_items * d]
+ *   has_features    DEVICE, uint8[n_items]
+ *   dtype           MF_F64
+ *   profiles        DEVICE, double[n_users * d]: output
+ *
+ * mf_content_normalize: out[r] = fl32(rows[r] / ||rows[r]||), the norm taken
+ * in FP64, a zero row where the norm is 0.  out_stride (0: d) is the row
+ * stride of `out` in floats, >= d; columns d .. out_stride - 1 are zeroed.
+ *   rows            DEVICE, double[n * d];  dtype MF_F64
+ *   out             DEVICE, float[n * out_stride]
+ *
+ * mf_content_similarity: S = X X^T for the n x d float32 rows X (the cosine
+ * when the rows are mf_content_normalize's), on v_mfma_f32_32x32x2_f32: each
+ * entry is one f32 fmaf chain in k order.  Only the 128 x 128 tiles on or
+ * above the diagonal are computed and each is written to both places:
+ * S[a,b] and S[b,a] are the same bits, and a zero row gives exact zeros.
+ * Nothing but S is allocated.
+ *   rows            DEVICE, float[n * d];  dtype MF_F32
+ *   similarity      DEVICE, float[n * n]: output
+ */
+int mf_content_profiles(const int64_t* user_ptr, const int32_t* item_ids, const void* weights,
+                        const void* features, const uint8_t* has_features, int32_t n_users,
+                        int32_t n_items, int32_t d, int32_t dtype, void* profiles, void* stream);
+int mf_content_normalize(const void* rows, int64_t n, int32_t d, int32_t out_stride,
+                         int32_t dtype, void* out, void* stream);
+int mf_content_similarity(const void* rows, int32_t n, int32_t d, int32_t dtype,
+                          void* similarity, void* stream);
+
 /* ---------------- BPR: Bayesian personalised ranking ---------------------- */
 
 /*

@@ -18,14 +18,19 @@ from the sparse ratings (mf_cf_stats, mf_cf_similarity) and a
 top-n_neighbors weighted prediction (mf_cf_predict); with
 ``stored_neighbors=M`` each entity's M best neighbours in place of the matrix
 (mf_cf_neighbours, mf_cf_*_nbr), for entity counts whose matrix does not fit.
-The content-based model
-of the reference is outside this build's scope.
+ContentBasedRecommender is the reference's content-based model
+(content_based.py): rating-weighted feature profiles and the item x item
+feature cosine built on the GPU (mf_content_profiles, mf_content_normalize,
+mf_content_similarity), the reference's placeholder prediction by default and
+two opt-in scorings (cosine retrieval through mf_predict / mf_topk / mf_rank,
+similarity-weighted prediction through the mf_cf_* kernels).
 """
 
 from .als_matrix_factorization import ALSMF
 from .baseline_model import BaselineModel
 from .bpr_matrix_factorization import BPRMF
 from .collaborative_filtering import ItemItemCF, UserUserCF
+from .content_based import ContentBasedRecommender
 from .implicit_als_matrix_factorization import ImplicitALSMF
 from .kernel_matrix_factorization import KernelMF
 from .recommender_base import RecommenderBase
@@ -35,6 +40,7 @@ __all__ = [
     "ALSMF",
     "BPRMF",
     "BaselineModel",
+    "ContentBasedRecommender",
     "ImplicitALSMF",
     "ItemItemCF",
     "KernelMF",

@@ -173,6 +173,11 @@ SIGNATURES = {
     "mf_cf_rank_nbr": (ctypes.c_int, [
         _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _F64, _I32,
         _P, _P, _P, _P, _P, _P, _P, _P]),
+    # content-based: profiles, row normalisation, feature cosine
+    "mf_content_profiles": (ctypes.c_int, [
+        _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),   # CSR, F, has, nu ni d dtype, out
+    "mf_content_normalize": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P]),
+    "mf_content_similarity": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P]),
     "mf_bpr_max_factors": (ctypes.c_int32, []),
     "mf_bpr_sample": (ctypes.c_int, [
         _P, _P, _P, _I64, _P, _P, _I32, _I32,         # order, positives, n, CSR, n_users n_items

@@ -76,13 +76,22 @@ class NeighbourEngine:
     device tensor, n_entities x n_entities).  With ``stored_neighbors=M`` S is
     None and nbr_ids (int32) / nbr_sims (float32), n_entities x M device
     tensors, hold each entity's M best neighbours by id ascending (-1 / 0
-    padding)."""
+    padding).  ``similarity=`` (a float32 device tensor, n_entities x
+    n_entities) is taken as S in place of mf_cf_similarity's."""
 
     def __init__(self, ent: np.ndarray, oth: np.ndarray, r: np.ndarray, n_entities: int,
                  n_others: int, device=None,
                  max_similarity_bytes: int = DEFAULT_MAX_SIMILARITY_BYTES,
-                 pass_cols: int = 0, what: str = "entities", stored_neighbors=None):
+                 pass_cols: int = 0, what: str = "entities", stored_neighbors=None,
+                 similarity=None):
         self.stored = None if stored_neighbors is None else int(stored_neighbors)
+        if similarity is not None:
+            if self.stored is not None:
+                raise ValueError("a precomputed similarity is dense: stored_neighbors must be None")
+            if (not isinstance(similarity, torch.Tensor) or similarity.dtype != torch.float32
+                    or tuple(similarity.shape) != (int(n_entities), int(n_entities))):
+                raise ValueError(f"similarity must be a float32 tensor of shape "
+                                 f"({n_entities}, {n_entities})")
         if self.stored is None:
             check_similarity_bytes(n_entities, max_similarity_bytes, what)
         else:
@@ -113,7 +122,10 @@ class NeighbourEngine:
                      self.n_entities, self.n_others, _lib.MF_F32, _tp(self.mean), _tp(self.norm),
                      int(pass_cols))
             self.S = self.nbr_ids = self.nbr_sims = None
-            if self.stored is None:
+            if similarity is not None:
+                # the caller's matrix in place of the rating similarity
+                self.S = similarity.to(self.dev).contiguous()
+            elif self.stored is None:
                 self.S = torch.empty((self.n_entities, self.n_entities), dtype=torch.float32,
                                      device=self.dev)
                 _lib.call("mf_cf_similarity", *lists, _tp(self.S), self.stream)
