@@ -206,6 +206,7 @@ void touch_strata_f32(hipStream_t s);
 void touch_strata_f64(hipStream_t s);
 void touch_bias(hipStream_t s);
 void touch_topk(hipStream_t s);
+void touch_topk_mm(hipStream_t s);
 void touch_als(hipStream_t s);
 void touch_ials(hipStream_t s);
 void touch_ials_cg(hipStream_t s);

@@ -1,4 +1,5 @@
-// mf_order.hpp -- the ranking order shared by top-k (mf_topk.hip) and exact
+// mf_order.hpp -- the ranking order shared by top-k (mf_topk.hip, its MFMA
+// filter mf_topk_mm.hip) and exact
 // ranking (mf_rank.hip): candidates go by score descending, then by item id
 // ascending, with NaN below every number; and the sorted-list searches both
 // use for the per-query exclusion CSR.
@@ -22,6 +23,35 @@ __device__ __forceinline__ double key_score(uint64_t k) {
 // (key desc, id asc): does (ka, ia) come before (kb, ib)?
 __device__ __forceinline__ bool cand_before(uint64_t ka, int32_t ia, uint64_t kb, int32_t ib) {
     return ka > kb || (ka == kb && ia < ib);
+}
+
+// The largest amount the fused exact path (k_topk_fused, mf_topk.hip) and the
+// MFMA filter in front of it (mf_topk_mm.hip) take.
+constexpr int kFusedMaxAmount = 64;
+
+// bitonic sort of n (power of two) candidates in LDS by the whole workgroup
+// subset `lanes` (threads t < lanes participate; all threads hit the barriers).
+// k_topk_merge's order: k_topk_mm_merge sorts with it too, so the filter's
+// output is the exact path's.
+__device__ __forceinline__ void cand_sort(uint64_t* key, int32_t* id, int n, int t, int lanes) {
+    for (int sz = 2; sz <= n; sz <<= 1) {
+        for (int st = sz >> 1; st > 0; st >>= 1) {
+            for (int x = t; x < n && t < lanes; x += lanes) {
+                const int y = x ^ st;
+                if (y > x) {
+                    const bool desc = (x & sz) == 0;
+                    const uint64_t kx = key[x], ky = key[y];
+                    const int32_t ix = id[x], iy = id[y];
+                    const bool xfirst = cand_before(kx, ix, ky, iy);
+                    if (desc ? !xfirst : xfirst) {
+                        key[x] = ky; key[y] = kx;
+                        id[x] = iy; id[y] = ix;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
 }
 
 // is `it` in the sorted id range items[lo, hi)?

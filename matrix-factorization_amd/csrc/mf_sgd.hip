@@ -283,6 +283,7 @@ extern "C" int mf_warmup(int32_t flags, void* stream) {
     lt.mark("warmup: strata units");
     touch_bias(s);
     touch_topk(s);
+    touch_topk_mm(s);
     touch_als(s);
     touch_ials(s);
     touch_ials_cg(s);

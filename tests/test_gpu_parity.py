@@ -376,6 +376,31 @@ def test_topk_mfma_filter_equals_exact(k, amount, bf16, monkeypatch):
         assert not set(mi[q]) & set(ex_items[ex_ptr[q]:ex_ptr[q + 1]])
 
 
+@pytest.mark.parametrize("bf16", ["1", "0"])
+@pytest.mark.parametrize("amount", [10, 16])
+def test_topk_mfma_filter_small_catalogue_no_probe(amount, bf16, monkeypatch):
+    """A catalogue under 128 items has no probe items (one per group of at
+    least 128 ids), so k_topk_mw runs without its probe walk and admission
+    floor: 100 items in one split, amount up to k_topk_mw's largest (16),
+    unknown users (-1), CSR exclusions of 0 to 20 items per user.  Same ids
+    and scores as mf_topk, no excluded item returned, bf16 and f32 operands."""
+    monkeypatch.setenv("MF_TOPK_BF16", bf16)
+    k, nu, ni = 16, 70, 100
+    eng = _topk_engine(k, nu, ni, 61)
+    rs = np.random.RandomState(amount)
+    users = rs.permutation(nu).astype(np.int32)
+    users[[3, 31, 64]] = -1
+    cnt = rs.randint(0, 21, nu)
+    ex_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    ex_items = np.concatenate([rs.choice(ni, c, replace=False) for c in cnt]).astype(np.int32)
+    mi, ms, ei, es, _ = _topk_both(eng, users, amount, ex_ptr, ex_items)
+    assert np.array_equal(mi, ei)
+    assert np.array_equal(ms, es)
+    assert (mi >= 0).all()                  # at least 80 candidates per user
+    for q in range(nu):
+        assert not set(mi[q]) & set(ex_items[ex_ptr[q]:ex_ptr[q + 1]])
+
+
 def test_topk_mfma_filter_ties_and_overflow():
     """Masses of exactly equal scores (duplicated items, all-zero users):
     ties keep the lower item id as in mf_topk; where a band outgrows its

@@ -1,5 +1,5 @@
 // tools/bf16_mfma_probe.hip -- numerics of v_mfma_f32_32x32x16_bf16 on this
-// GPU, for k_topk_mw's error bound (mf_topk.hip): are bf16 x bf16 products
+// GPU, for k_topk_mw's error bound (mf_topk_mm.hip): are bf16 x bf16 products
 // exact, how are the 16 products and the f32 accumulator summed (rounding),
 // and the worst |mfma - exact| / sum |a b| over random data.
 // Build: hipcc -O2 --offload-arch=gfx950 tools/bf16_mfma_probe.hip -o tools/bf16_mfma_probe
