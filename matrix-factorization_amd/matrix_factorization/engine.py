@@ -1016,7 +1016,13 @@ class SGDEngine:
         # now, not in the first epoch
         if self.n:
             self._ensure_strata_ws(plan.B, plan.n_strata)
-            self._prime_strata(plan)
+            try:
+                self._prime_strata(plan)
+            except _lib.MFLibraryError:
+                # a plan the launcher refuses (rank 0, say) is not kept: the
+                # engine is as before the call
+                self.strata, self._regroups = None, []
+                raise
         return plan
 
     def _prime_strata(self, pl) -> None:
@@ -1702,6 +1708,27 @@ class SGDEngine:
                 self.dcode, self.gamma, self.min_rating, self.max_rating, _np(offs),
                 0 if offs is None else len(offs) - 1)
 
+    def strata_kernel_attrs(self, sub) -> tuple:
+        """The kernel that the persistent launch of plan ``sub`` (a
+        StrataPlan: the engine's, or one phase of it) runs with the engine's
+        current settings, as (registers per thread, waves per workgroup, LDS
+        bytes: dynamic + static); (0, 0, 0) where the epoch would run as one
+        launch per stratum.  No launch (MF_FLAG_PREPARE), the parameters
+        untouched."""
+        attrs = (ctypes.c_int32 * 3)()
+        seq = np.arange(sub.n_strata, dtype=np.int32)
+        flags = self._strata_flags(sub, True) | _lib.MF_FLAG_PREPARE
+        self._ensure_strata_ws(sub.B, len(seq))
+        with torch.cuda.device(self.dev):
+            _lib.call("mf_sgd_epoch_strata_ticket", _tp(sub.d_u), _tp(sub.d_i), _tp(sub.d_r),
+                      sub.n_positions, sub.B, _tp(sub.d_ubnd), _tp(sub.d_ibnd), _tp(sub.d_bstep),
+                      sub.NS, sub.max_items, sub.max_users, _np(seq), len(seq), 0,
+                      self.global_mean, None, None, None, None, self.n_users, self.n_items,
+                      self.k, self.kcode, self.dcode, self.gamma, 0.0, 0.0, self.min_rating,
+                      self.max_rating, 1, 1, flags, _tp(self._strata_ws),
+                      self._strata_ws.numel() * 4, None, 0, attrs, self.stream, None)
+        return tuple(attrs)
+
     def _beside_state(self):
         """The beside-mode state of this engine (built at first use), or None
         where the mode cannot apply: no factor model, no strata plan, a
@@ -1725,21 +1752,11 @@ class SGDEngine:
                     if s.n_positions), None)
         if sub is None:
             return None
-        sweep, apass = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)()
+        apass = (ctypes.c_int32 * 3)()
         with torch.cuda.device(self.dev):
             if not _lib.load().mf_beside_supported():
                 return None
-            # the kernel the plan's persistent launch runs (no launch)
-            seq = np.arange(sub.n_strata, dtype=np.int32)
-            flags = self._strata_flags(sub, True) | _lib.MF_FLAG_PREPARE
-            self._ensure_strata_ws(sub.B, len(seq))
-            _lib.call("mf_sgd_epoch_strata_ticket", _tp(sub.d_u), _tp(sub.d_i), _tp(sub.d_r),
-                      sub.n_positions, sub.B, _tp(sub.d_ubnd), _tp(sub.d_ibnd), _tp(sub.d_bstep),
-                      sub.NS, sub.max_items, sub.max_users, _np(seq), len(seq), 0,
-                      self.global_mean, None, None, None, None, self.n_users, self.n_items,
-                      self.k, self.kcode, self.dcode, self.gamma, 0.0, 0.0, self.min_rating,
-                      self.max_rating, 1, 1, flags, _tp(self._strata_ws),
-                      self._strata_ws.numel() * 4, None, 0, sweep, self.stream, None)
+            sweep = self.strata_kernel_attrs(sub)
             _lib.call("mf_sse_beside", None, 0, *self._sse_args(self.P, self.Q, self.bu, self.bi),
                       _tp(self.ws), _VOID(self.sse_buf.data_ptr()), self.stream, apass)
             info = dict(sweep=tuple(sweep), sse=tuple(apass))

@@ -23,9 +23,12 @@ multiple of 4 and of 2, so it is a tail rank of (4,16,2) / (2,16,4), not of
 the W = 1 branch; 101 covers (1,64,2).
 
 The engine level on purpose: ``SGDEngine`` directly, a few thousand ratings,
-so a failure names one layout of one kernel.  Follow-up, not covered here:
-the strata sweep and ``KernelMF.fit()`` at ranks > 128 (the strata planner,
-its LDS budgets and the two plans).
+so a failure names one layout of one kernel.  The strata sweep in every
+layout and launch form, and the strata planner with its LDS budgets at wide
+ranks, are covered the same way by tests/test_gpu_strata_layouts.py; the
+layout tables, the NumPy float32 sweep and the FP32 bound used by both files
+live in tests/row_layouts_reference.py.  Follow-up, not covered by either:
+``KernelMF.fit()`` itself at ranks > 128.
 
 FP32 bounds (checks 2 to 4).  The FP32 kernels are compared value by value
 with the FP64 oracle run on the FP32-rounded inputs.  The tolerance is a
@@ -69,39 +72,19 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from row_layouts_reference import (EPS32, ROWS_SCALAR, ROWS_WIDE, SGD_RANKS, WV,  # noqa: F401
+                                   W1_RANKS, all_rows_layouts, assert_fp32_close, kpad_of,
+                                   layout_representatives, numpy_sgd_sweep, rows_layout)
+from row_layouts_reference import maxabs as _maxabs
 
 gpu = pytest.mark.gpu
 
 KERNELS = ("linear", "sigmoid", "rbf")
 LR, REG, LO, HI = 0.01, 0.02, 1.0, 5.0
-EPS32 = float(np.finfo(np.float32).eps)
 M = 4          # see the module docstring
 
 # ---------------------------------------------------------------- layouts
-ROWS_WIDE = {1: (1, 1), 2: (2, 1), 4: (4, 1), 8: (8, 1), 16: (16, 1), 32: (16, 2),
-             64: (16, 4), 128: (16, 8), 256: (16, 16)}              # kvp -> (GS, V)
-ROWS_SCALAR = {16: (16, 1), 32: (32, 1), 64: (64, 1), 128: (64, 2), 256: (64, 4),
-               512: (64, 8), 1024: (64, 16)}                        # kpad -> (GS, V)
 READ_TABLE = dict(ROWS_SCALAR)                                      # dispatch: kpad -> (GS, V)
-WV = {"float32": 4, "float64": 2}
-
-
-def kpad_of(k):
-    kp = 16
-    while kp < k:
-        kp <<= 1
-    return kp
-
-
-def rows_layout(dtype, k):
-    """(W, GS, V) of dispatch_rows."""
-    wv = WV[dtype]
-    if k > 0 and k % wv == 0 and k // wv <= 256:
-        kvp = 1
-        while kvp < k // wv:
-            kvp <<= 1
-        return (wv,) + ROWS_WIDE[kvp]
-    return (1,) + ROWS_SCALAR[kpad_of(k)]
 
 
 def read_layout(k):
@@ -109,38 +92,11 @@ def read_layout(k):
     return READ_TABLE[kpad_of(k)]
 
 
-def all_rows_layouts(dtype):
-    return ({(WV[dtype],) + v for v in ROWS_WIDE.values()} |
-            {(1,) + v for v in ROWS_SCALAR.values()})
-
-
-W1_RANKS = [1, 3, 17, 33, 101, 129, 257, 513, 1023]
-# the full-width rank of every W > 1 layout, then a tail rank of each one that
-# can have a tail (kvp >= 4), then the W = 1 ranks (all of them tails but FP64
-# 1024); 0 = biases only
-SGD_RANKS = {
-    "float32": [0, 4, 8, 16, 32, 64, 128, 256, 512, 1024,
-                12, 20, 40, 100, 132, 260, 516] + W1_RANKS,
-    "float64": [0, 2, 4, 8, 16, 32, 64, 128, 256, 512,
-                6, 10, 18, 34, 100, 130, 260] + W1_RANKS + [1024],
-}
 # every read layout at its full width and at a tail rank
 READ_RANKS = [12, 16, 20, 32, 40, 64, 100, 128, 200, 256, 300, 512, 1000, 1024]
 # one tail rank per W: the frozen-side runs
 FROZEN_RANKS = {"float32": [132, 1023], "float64": [260, 1023]}
 MM_RANKS = [12, 16, 20, 32, 40, 64]        # mf_topk_mm_supported: FP32, linear, these of READ_RANKS
-
-
-def layout_representatives(dtype):
-    """One rank per layout of dispatch_rows: the last of SGD_RANKS that takes
-    it with a tail, else the last that takes it."""
-    best = {}
-    for k in SGD_RANKS[dtype]:
-        w, gs, v = lay = rows_layout(dtype, k)
-        tail = 0 < k < w * gs * v
-        if lay not in best or tail >= best[lay][0]:
-            best[lay] = (tail, k)
-    return sorted(k for _, k in best.values())
 
 
 # ------------------------------------------------------------------ data
@@ -196,62 +152,7 @@ def _figure(line):
         print(line)
 
 
-def _maxabs(a):
-    return float(np.max(np.abs(a))) if a.size else 0.0
-
-
 # ------------------------------------------- NumPy restatements (any dtype)
-def numpy_sgd_sweep(u, i, r, mu, bu, bi, P, Q, kernel, gamma, lr, reg, lo, hi, order, dtype,
-                    update_user=True, update_item=True):
-    """One sequential sweep over ``order`` in ``dtype`` arithmetic: the
-    reference's per-rating bodies (kernels.py:108-327) in its expression
-    order, as csrc/mf_rows.hpp restates them in sgd_error / sgd_bias /
-    sgd_rows, every operation rounded on its own (no fused multiply-add),
-    ``np.exp`` of ``dtype``.  Returns new (P, Q, b_u, b_i) as float64."""
-    T = np.dtype(dtype).type
-    P, Q, bu, bi = (np.array(a, dtype=T) for a in (P, Q, bu, bi))
-    r = np.asarray(r, T)
-    mu, gamma, lr, reg = T(mu), T(gamma), T(lr), T(reg)
-    a, c = T(lo), T(hi - lo)
-    one, two = T(1), T(2)
-    for j in order:
-        x, y = u[j], i[j]
-        p, q = P[x].copy(), Q[y].copy()
-        if kernel == "rbf":
-            df = p - q
-            E = np.exp((-gamma) * np.sum(df * df, dtype=T))
-            e = (a + c * E) - r[j]
-            d = (two * E) * gamma
-            if update_user:
-                P[x] = p - lr * (e * (d * (q - p)) + reg * p)
-            if update_item:
-                Q[y] = q - lr * (e * (d * (p - q)) + reg * q)
-            continue
-        ub, ib = bu[x], bi[y]
-        dot = np.sum(p * q, dtype=T)
-        if kernel == "linear":
-            e = (((mu + ib) + ub) + dot) - r[j]
-            if update_user:
-                bu[x] = ub - lr * (e + reg * ub)
-                P[x] = p - lr * (e * q + reg * p)
-            if update_item:
-                bi[y] = ib - lr * (e + reg * ib)
-                Q[y] = q - lr * (e * p + reg * q)
-        else:
-            lin = ((mu + ub) + ib) + dot
-            ex = np.exp(-lin)
-            sg = one / (one + ex)
-            e = (a + c * sg) - r[j]
-            d = (sg * sg) * ex
-            if update_user:
-                bu[x] = ub - lr * (e * d + reg * ub)
-                P[x] = p - lr * (e * (q * d) + reg * p)
-            if update_item:
-                bi[y] = ib - lr * (e * d + reg * ib)
-                Q[y] = q - lr * (e * (p * d) + reg * q)
-    return tuple(np.asarray(a, np.float64) for a in (P, Q, bu, bi))
-
-
 def numpy_predict(u, i, mu, bu, bi, P, Q, kernel, gamma, lo, hi, dtype, bound=False):
     """predict_one (kernels.py:21-105) for id pairs in ``dtype`` arithmetic
     (-1: zero row, zero bias); float64 result."""
@@ -425,19 +326,7 @@ def _assert_fp64_close(got, ref):
         assert err <= 1e-11 * scale, f"{name}: max |diff| {err:.3e} > 1e-11 * {scale:.3g}"
 
 
-def _assert_fp32_close(tag, got, n32, ref):
-    """max|gpu - ref| <= M d32 + 4 eps32 max|ref| per array; prints the figures."""
-    bad = []
-    for name, g, n, rf in zip(("P", "Q", "bu", "bi"), got, n32, ref):
-        assert g.shape == rf.shape
-        d32, dev, scale = _maxabs(n - rf), _maxabs(g - rf), _maxabs(rf)
-        ratio = dev / d32 if d32 > 0 else (0.0 if dev == 0 else float("inf"))
-        _figure(f"ROWLAYOUT {tag} {name} d32={d32:.3e} gpu={dev:.3e} ratio={ratio:.3f} "
-              f"scale={scale:.3e}")
-        assert M * d32 <= 1e-4 * scale, f"{name}: vacuous bound, d32 = {d32:.3e}"
-        if not dev <= M * d32 + 4 * EPS32 * scale:
-            bad.append(f"{name}: max |diff| {dev:.3e} > {M} * {d32:.3e} + 4 eps32 * {scale:.3g}")
-    assert not bad, "; ".join(bad)
+_assert_fp32_close = functools.partial(assert_fp32_close, m=M, figure=_figure)
 
 
 @gpu
