@@ -993,6 +993,74 @@ int mf_content_normalize(const void* rows, int64_t n, int32_t d, int32_t out_str
 int mf_content_similarity(const void* rows, int32_t n, int32_t d, int32_t dtype,
                           void* similarity, void* stream);
 
+/* ---------------- Hybrid: embedding retrieval, model rerank --------------- */
+
+/*
+ * HybridRecommender's second stage (hybrid.py; the reference's
+ * project_template/pipeline/evaluate_hybrid.py:133-153): per query, the
+ * n_cand candidates an embedding retrieval returned (index rows and their
+ * float32 similarities, in retrieval order; mf_topk's output) are filtered,
+ * scored by the factor model, blended and reordered.  One workgroup per query;
+ * nothing of size n_query x n_rows is touched.
+ *
+ *  1. kept: position c is kept when 0 <= cand_rows[c] < n_rows and the row is
+ *     not in the query's exclusion list (binary search; each list sorted
+ *     ascending).  Kept positions stay in retrieval order; out_n_cand[q] = m,
+ *     their count.  Dropping happens after the retrieval, as in the reference,
+ *     so m can be below n_cand.
+ *  2. model score: s_c = (float) mf_predict(query_users[q], item of the row,
+ *     bound_ratings = 0), bit for bit; the item is row_item[row] (row_item
+ *     null: the row itself), and a user or item that is negative (an item also
+ *     when >= n_items) reads as a zero row and zero bias.  user_features
+ *     null: no model, s_c = 0 (dtype, kernel and n_factors are still checked).
+ *  3. min-max (evaluate_hybrid.py:72-79) of the model scores and of the
+ *     similarities, each over the kept candidates: with lo / hi their min /
+ *     max, every value is 0 when (double)hi - (double)lo < 1e-8, else
+ *     fl32(fl32(x - lo) / fl32((double)hi - (double)lo)); a NaN among the kept
+ *     values makes the whole term NaN (np.min).
+ *  4. score = fl32(fl32(fl32(alpha) * a) + fl32(fl32(1.0 - alpha) * b)), a the
+ *     model term and b the similarity term, 1.0 - alpha taken in double: NumPy's
+ *     float32 result of alpha * a + (1.0 - alpha) * b.  A score of -0 is
+ *     written as +0.
+ *  5. order: score descending, then position in the retrieval order
+ *     ascending, NaN last -- the STABLE order; the reference's
+ *     np.argsort(-score) leaves the order of equal scores unspecified.  The
+ *     first `amount` are written, the rest of each output row is padded with
+ *     row -1 and NaN.
+ * No float32 operation is contracted, counting and ordering are integer and
+ * compare only: the same inputs give the same bytes whatever the grid.
+ *
+ *   query_users     DEVICE, int32[n_query]: the MODEL's internal user ids
+ *   cand_rows       DEVICE, int32[n_query * n_cand]; -1 entries are skipped
+ *   cand_sims       DEVICE, float[n_query * n_cand]
+ *   n_cand          1 .. 2048 (mf_topk's largest amount)
+ *   row_item        DEVICE, int32[n_rows], nullable
+ *   user_biases .. max_rating   the model, as for mf_predict
+ *   exclude_ptr / exclude_rows  DEVICE CSR of index rows per query, nullable
+ *   alpha           finite
+ *   amount          0 .. n_cand
+ *   workspace       mf_hybrid_rerank_workspace_bytes() bytes (0: may be null)
+ *   out_rows / out_scores       DEVICE, [n_query * amount]
+ *   out_model / out_sims        DEVICE, nullable, same shape: s_c and the raw
+ *                               similarity of each output
+ *   out_n_cand      DEVICE, int32[n_query]
+ * Invalid arguments (dtype, kernel, n_factors as for mf_predict; n_cand,
+ * amount, a non-finite alpha, negative counts) return MF_ERR_INVALID before
+ * any device work, the argument's name in mf_last_error(); n_query == 0
+ * returns MF_OK.
+ */
+size_t mf_hybrid_rerank_workspace_bytes(int32_t n_query, int32_t n_cand);
+int mf_hybrid_rerank(const int32_t* query_users, int32_t n_query, const int32_t* cand_rows,
+                     const float* cand_sims, int32_t n_cand, const int32_t* row_item,
+                     int32_t n_rows, double global_mean, const void* user_biases,
+                     const void* item_biases, const void* user_features,
+                     const void* item_features, int32_t n_items, int32_t n_factors,
+                     int32_t kernel, int32_t dtype, double gamma, double min_rating,
+                     double max_rating, const int64_t* exclude_ptr, const int32_t* exclude_rows,
+                     double alpha, int32_t amount, void* workspace, int32_t* out_rows,
+                     float* out_scores, float* out_model, float* out_sims, int32_t* out_n_cand,
+                     void* stream);
+
 /* ---------------- BPR: Bayesian personalised ranking ---------------------- */
 
 /*

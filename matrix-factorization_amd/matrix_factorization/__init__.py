@@ -24,6 +24,10 @@ feature cosine built on the GPU (mf_content_profiles, mf_content_normalize,
 mf_content_similarity), the reference's placeholder prediction by default and
 two opt-in scorings (cosine retrieval through mf_predict / mf_topk / mf_rank,
 similarity-weighted prediction through the mf_cf_* kernels).
+HybridRecommender is the path the reference's project_template ships
+(pipeline/evaluate_hybrid.py): candidates retrieved by embedding cosine
+(profiles and mf_topk as above), then filtered, scored by a fitted factor model
+and blended with the cosine in one pass per user (mf_hybrid_rerank).
 """
 
 from .als_matrix_factorization import ALSMF
@@ -31,6 +35,7 @@ from .baseline_model import BaselineModel
 from .bpr_matrix_factorization import BPRMF
 from .collaborative_filtering import ItemItemCF, UserUserCF
 from .content_based import ContentBasedRecommender
+from .hybrid import HybridRecommender
 from .implicit_als_matrix_factorization import ImplicitALSMF
 from .kernel_matrix_factorization import KernelMF
 from .recommender_base import RecommenderBase
@@ -41,6 +46,7 @@ __all__ = [
     "BPRMF",
     "BaselineModel",
     "ContentBasedRecommender",
+    "HybridRecommender",
     "ImplicitALSMF",
     "ItemItemCF",
     "KernelMF",

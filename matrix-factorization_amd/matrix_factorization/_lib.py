@@ -178,6 +178,13 @@ SIGNATURES = {
         _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),   # CSR, F, has, nu ni d dtype, out
     "mf_content_normalize": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P]),
     "mf_content_similarity": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P]),
+    # hybrid: model rerank of retrieved candidates
+    "mf_hybrid_rerank_workspace_bytes": (ctypes.c_size_t, [_I32, _I32]),
+    "mf_hybrid_rerank": (ctypes.c_int, [
+        _P, _I32, _P, _P, _I32, _P, _I32,             # users, nq, cand rows, sims, n_cand, row_item, n_rows
+        _F64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F64, _F64, _F64,   # the model, as mf_predict
+        _P, _P, _F64, _I32, _P,                       # exclusions, alpha, amount, ws
+        _P, _P, _P, _P, _P, _P]),                     # rows, scores, model, sims, n_cand, stream
     "mf_bpr_max_factors": (ctypes.c_int32, []),
     "mf_bpr_sample": (ctypes.c_int, [
         _P, _P, _P, _I64, _P, _P, _I32, _I32,         # order, positives, n, CSR, n_users n_items
