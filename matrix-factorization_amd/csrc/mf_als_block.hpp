@@ -234,12 +234,7 @@ inline int check_ials_args(const char* fn, const int64_t* entity_ptr, const int3
     const void* need[] = {entity_ptr, other_ids, strengths, other_features, gram, features};
     const char* names[] = {"entity_ptr", "other_ids", "strengths", "other_features", "gram",
                            "features"};
-    for (int i = 0; i < 6; ++i)
-        if (!need[i]) {
-            set_error("%s: %s is NULL", fn, names[i]);
-            return MF_ERR_INVALID;
-        }
-    return MF_OK;
+    return null_arg(fn, need, names, 6) ? MF_ERR_INVALID : MF_OK;
 }
 
 }  // namespace alsblk

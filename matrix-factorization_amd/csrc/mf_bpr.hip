@@ -235,15 +235,6 @@ struct EpochLaunch {
     }
 };
 
-inline bool null_arg(const char* fn, const void* const* need, const char* const* names, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!need[i]) {
-            set_error("%s: %s is NULL", fn, names[i]);
-            return true;
-        }
-    return false;
-}
-
 }  // namespace bpr
 }  // namespace mf
 
@@ -276,7 +267,7 @@ extern "C" int mf_bpr_sample(const int32_t* order, const int32_t* pos_users,
     }
     const void* need[] = {pos_users, pos_items, user_ptr, user_items, neg_items};
     const char* names[] = {"pos_users", "pos_items", "user_ptr", "user_items", "neg_items"};
-    if (bpr::null_arg("mf_bpr_sample", need, names, 5)) return MF_ERR_INVALID;
+    if (null_arg("mf_bpr_sample", need, names, 5)) return MF_ERR_INVALID;
     bpr::SampleArgs a{order, pos_users, pos_items, user_ptr, user_items, neg_items, n_pos, seed,
                       (uint32_t)n_items};
     hipLaunchKernelGGL(bpr::k_bpr_sample, dim3((unsigned)((n_pos + kBlock - 1) / kBlock)),
@@ -349,10 +340,10 @@ extern "C" int mf_bpr_epoch(const int32_t* user_ids, const int32_t* item_ids,
                           item_features};
     const char* names[] = {"user_ids", "item_ids", "neg_items", "item_biases", "z_out",
                            "user_features", "item_features"};
-    if (bpr::null_arg("mf_bpr_epoch", need, names, n_factors > 0 ? 7 : 5)) return MF_ERR_INVALID;
+    if (null_arg("mf_bpr_epoch", need, names, n_factors > 0 ? 7 : 5)) return MF_ERR_INVALID;
     bpr::EpochLaunch L{user_ids, item_ids, neg_items, order, batch_offsets, batch_seq, n_launch,
                        item_biases, user_features, item_features, z_out, n_factors, lr, reg,
                        update_user_params ? 1 : 0, update_item_params ? 1 : 0,
                        (hipStream_t)stream};
-    return dispatch(dtype, n_factors, MF_LINEAR, L);
+    return dispatch("mf_bpr_epoch", dtype, n_factors, MF_LINEAR, L);
 }

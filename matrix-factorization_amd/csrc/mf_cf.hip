@@ -288,7 +288,7 @@ extern "C" int mf_cf_stats(const int64_t* entity_ptr, const void* ratings, int32
     if (n_entities == 0) return MF_OK;
     const void* need[] = {entity_ptr, mean, norm};
     const char* names[] = {"entity_ptr", "mean", "norm"};
-    if (cf::null_arg("mf_cf_stats", need, names, 3)) return MF_ERR_INVALID;
+    if (null_arg("mf_cf_stats", need, names, 3)) return MF_ERR_INVALID;
     hipLaunchKernelGGL(cf::k_cf_stats, dim3((unsigned)((n_entities + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, (hipStream_t)stream, entity_ptr,
                        static_cast<const float*>(ratings), n_entities, (double)n_others, mean,
@@ -396,7 +396,7 @@ extern "C" int mf_cf_similarity(const int64_t* entity_ptr, const int32_t* other_
     if (n_entities == 0) return MF_OK;
     const void* need[] = {entity_ptr, other_ptr, mean, norm, similarity};
     const char* names[] = {"entity_ptr", "other_ptr", "mean", "norm", "similarity"};
-    if (cf::null_arg("mf_cf_similarity", need, names, 5)) return MF_ERR_INVALID;
+    if (null_arg("mf_cf_similarity", need, names, 5)) return MF_ERR_INVALID;
     cf::SimArgs a;
     a.eptr = entity_ptr; a.eoth = other_ids; a.er = static_cast<const float*>(ratings);
     a.optr = other_ptr; a.oent = entity_ids; a.orr = static_cast<const float*>(other_ratings);
@@ -435,7 +435,7 @@ extern "C" int mf_cf_neighbours(const int64_t* entity_ptr, const int32_t* other_
     const void* need[] = {entity_ptr, other_ptr, mean, norm, workspace, nbr_ids, nbr_sims};
     const char* names[] = {"entity_ptr", "other_ptr", "mean", "norm", "workspace", "nbr_ids",
                            "nbr_sims"};
-    if (cf::null_arg("mf_cf_neighbours", need, names, 7)) return MF_ERR_INVALID;
+    if (null_arg("mf_cf_neighbours", need, names, 7)) return MF_ERR_INVALID;
     cf::NbrArgs a;
     a.sim.eptr = entity_ptr; a.sim.eoth = other_ids; a.sim.er = static_cast<const float*>(ratings);
     a.sim.optr = other_ptr; a.sim.oent = entity_ids;

@@ -177,14 +177,5 @@ inline bool bad_n_stored(const char* fn, int32_t n_stored) {
     return true;
 }
 
-inline bool null_arg(const char* fn, const void* const* need, const char* const* names, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!need[i]) {
-            set_error("%s: %s is NULL", fn, names[i]);
-            return true;
-        }
-    return false;
-}
-
 }  // namespace cf
 }  // namespace mf

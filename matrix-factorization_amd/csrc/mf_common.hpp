@@ -33,6 +33,16 @@ int hip_fail(hipError_t e, const char* what);
         if (_e != hipSuccess) return ::mf::hip_fail(_e, #expr); \
     } while (0)
 
+// true, with "<fn>: <name> is NULL" as the error, at the first NULL of need[0, n)
+inline bool null_arg(const char* fn, const void* const* need, const char* const* names, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!need[i]) {
+            set_error("%s: %s is NULL", fn, names[i]);
+            return true;
+        }
+    return false;
+}
+
 // Bijective XCD-aware block remap (guide T1).  Workgroups b, b+8, b+16, ...
 // are dealt to the same XCD; give that XCD a contiguous range of tiles so
 // neighbouring tiles (which touch neighbouring item rows after the colour

@@ -200,11 +200,11 @@ extern "C" int mf_content_profiles(const int64_t* user_ptr, const int32_t* item_
     if (n_users == 0 || d == 0) return MF_OK;
     const void* need[] = {user_ptr, profiles};
     const char* names[] = {"user_ptr", "profiles"};
-    if (cf::null_arg(fn, need, names, 2)) return MF_ERR_INVALID;
+    if (null_arg(fn, need, names, 2)) return MF_ERR_INVALID;
     if (n_items > 0) {                                // else every list is skipped
         const void* need2[] = {features, has_features};
         const char* names2[] = {"features", "has_features"};
-        if (cf::null_arg(fn, need2, names2, 2)) return MF_ERR_INVALID;
+        if (null_arg(fn, need2, names2, 2)) return MF_ERR_INVALID;
     }
     int G = 1;
     while (G < d && G < kWave) G <<= 1;
@@ -237,7 +237,7 @@ extern "C" int mf_content_normalize(const void* rows, int64_t n, int32_t d, int3
     if (n == 0 || stride == 0) return MF_OK;
     const void* need[] = {d ? rows : out, out};
     const char* names[] = {"rows", "out"};
-    if (cf::null_arg(fn, need, names, 2)) return MF_ERR_INVALID;
+    if (null_arg(fn, need, names, 2)) return MF_ERR_INVALID;
     hipLaunchKernelGGL(content::k_content_normalize,
                        dim3((unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0,
                        (hipStream_t)stream, static_cast<const double*>(rows), n, d, stride,
@@ -257,7 +257,7 @@ extern "C" int mf_content_similarity(const void* rows, int32_t n, int32_t d, int
     if (n == 0) return MF_OK;
     const void* need[] = {d ? rows : similarity, similarity};
     const char* names[] = {"rows", "similarity"};
-    if (cf::null_arg(fn, need, names, 2)) return MF_ERR_INVALID;
+    if (null_arg(fn, need, names, 2)) return MF_ERR_INVALID;
     const unsigned nb = (unsigned)((n + content::kTile - 1) / content::kTile);
     if (nb > 65535u) {
         set_error("%s: n=%d needs %u tile rows (at most 65535)", fn, n, nb);

@@ -6,21 +6,25 @@
 namespace mf {
 
 // ------------------------------------------------------------ dispatch
+// What dispatch() can serve, refused in entry point fn's name.  An entry point
+// that returns early for empty input calls this first, so that bad codes are
+// refused whatever the sizes.
+inline int check_model(const char* fn, int dtype, int k, int kernel) {
+    if (dtype != MF_F32 && dtype != MF_F64)
+        set_error("%s: dtype=%d (must be MF_F32 or MF_F64)", fn, dtype);
+    else if (kernel < MF_LINEAR || kernel > MF_RBF)
+        set_error("%s: kernel=%d (must be MF_LINEAR, MF_SIGMOID or MF_RBF)", fn, kernel);
+    else if (k < 0 || k > kMaxFactors)
+        set_error("%s: n_factors=%d (must be in [0, %d])", fn, k, kMaxFactors);
+    else
+        return MF_OK;
+    return MF_ERR_INVALID;
+}
+
 // Calls F.template run<T, GS, V, KERN>() for the runtime (dtype, k, kernel).
 template <typename F>
-inline int dispatch(int dtype, int k, int kernel, F&& f) {
-    if (k < 0 || k > kMaxFactors) {
-        set_error("n_factors=%d outside [0, %d]", k, kMaxFactors);
-        return MF_ERR_INVALID;
-    }
-    if (kernel < MF_LINEAR || kernel > MF_RBF) {
-        set_error("unknown kernel code %d", kernel);
-        return MF_ERR_INVALID;
-    }
-    if (dtype != MF_F32 && dtype != MF_F64) {
-        set_error("unknown dtype code %d", dtype);
-        return MF_ERR_INVALID;
-    }
+inline int dispatch(const char* fn, int dtype, int k, int kernel, F&& f) {
+    if (check_model(fn, dtype, k, kernel) != MF_OK) return MF_ERR_INVALID;
     const int kp = kpad_of(k);
 #define MF_KCASE(T, KP, GS, V)                                                   \
     if (kp == KP) {                                                              \

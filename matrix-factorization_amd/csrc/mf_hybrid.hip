@@ -7,10 +7,9 @@
 //   1. kept candidates: positions whose index row is in range and not in the
 //      query's sorted exclusion list, compacted in retrieval order (ballot
 //      prefix per wave, wave totals through LDS);
-//   2. model score of each kept row's item: predict's arithmetic (lane
-//      partials of the (GS, V) layout, group_sum<GS>, predict_one's
-//      expression), cast to float32; the user's row stays in registers and a
-//      wave scores 64 / GS candidates per step;
+//   2. model score of each kept row's item: mf_predict's value (score_pair
+//      of mf_score.hpp), cast to float32; the user's row stays in registers
+//      and a wave scores 64 / GS candidates per step;
 //   3. min and max of the model scores and of the similarities (wave shuffles
 //      plus LDS), min-max normalisation and the blend in float32, nothing
 //      contracted;
@@ -24,7 +23,7 @@
 // depend on the launch.
 #include <cmath>
 
-#include "mf_common.hpp"
+#include "mf_score.hpp"
 #include "mf_order.hpp"
 
 namespace mf {
@@ -33,12 +32,10 @@ constexpr int kHybridMaxCand = 2048;                 // mf_topk's cap on amount
 
 template <typename T>
 struct HybridArgs {
+    ModelView<T> m;                                   // m.P == nullptr: no model, scores 0
     const int32_t* users; int32_t nq;
     const int32_t* cand_rows; const float* cand_sims; int32_t n_cand;
     const int32_t* row_item; int32_t n_rows;
-    const T* P; const T* Q; const T* Bu; const T* Bi;
-    int32_t n_items, k;
-    Hyper<T> h;
     const int64_t* ex_ptr; const int32_t* ex_rows;
     float alpha, beta;                                // fl32(alpha), fl32(1.0 - alpha)
     int32_t amount, cap;                              // cap: LDS slots, a power of two >= n_cand
@@ -144,43 +141,17 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_rerank(HybridArgs<T> A) {
     if (t == 0) A.out_n_cand[qy] = m;
 
     // 2. model scores
-    if (A.P) {
-        const int32_t uu = A.users[qy];
-        const bool uk = uu >= 0;
+    if (A.m.P) {
         T p[V], bu;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const int f = l + v * GS;
-            p[v] = (uk && f < A.k) ? A.P[(int64_t)uu * A.k + f] : (T)0;
-        }
-        bu = (uk && KERN != MF_RBF) ? A.Bu[uu] : (T)0;
+        load_user<T, GS, V, KERN>(A.m, A.users[qy], l, p, bu);
         for (int jb = wv * R; jb < m; jb += kWavesPerBlock * R) {    // wave-uniform bound
             const int j = jb + g;
             const bool have = j < m;
             const int32_t row = have ? rows[j] : 0;
             const int32_t it = have ? (A.row_item ? A.row_item[row] : row) : -1;
-            const bool ok = it >= 0 && it < A.n_items;
-            const T* qr = A.Q + (int64_t)(ok ? it : 0) * A.k;
-            T s = (T)0;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const int f = l + v * GS;
-                const T qv = (ok && f < A.k) ? qr[f] : (T)0;
-                if constexpr (KERN == MF_RBF) {
-                    const T d = p[v] - qv;
-                    s = s + d * d;
-                } else {
-                    s = s + p[v] * qv;
-                }
-            }
-            const T bi = (ok && KERN != MF_RBF) ? A.Bi[it] : (T)0;
-            s = group_sum<GS>(s);
-            const Hyper<T>& h = A.h;
-            T pred;                                                  // predict_one (mf_rows.hpp)
-            if constexpr (KERN == MF_LINEAR) pred = ((h.mu + bi) + bu) + s;
-            else if constexpr (KERN == MF_SIGMOID)
-                pred = h.a + h.c * ((T)1 / ((T)1 + dexp<T>(-(((h.mu + bu) + bi) + s))));
-            else pred = h.a + h.c * dexp<T>((-h.gamma) * s);
+            T q[V], bi;
+            load_item<T, GS, V, KERN>(A.m, it, it >= 0 && it < A.m.n_items, l, q, bi);
+            const T pred = score_pair<T, GS, V, KERN>(A.m.h, p, bu, q, bi);
             if (have && l == 0) sm[j] = (float)pred;
         }
     } else {
@@ -234,8 +205,7 @@ struct HybridLaunch {
     const int32_t* users; int32_t nq;
     const int32_t* cand_rows; const float* cand_sims; int32_t n_cand;
     const int32_t* row_item; int32_t n_rows;
-    double mu; const void* bu; const void* bi; const void* P; const void* Q;
-    int32_t n_items; int32_t k; double gamma, lo, hi;
+    Model m;
     const int64_t* ex_ptr; const int32_t* ex_rows;
     double alpha; int32_t amount;
     int32_t* out_rows; float* out_scores; float* out_model; float* out_sims;
@@ -245,11 +215,9 @@ struct HybridLaunch {
     template <typename T, int GS, int V, int KERN>
     int run() {
         HybridArgs<T> a;
+        a.m = m.view<T>();
         a.users = users; a.nq = nq; a.cand_rows = cand_rows; a.cand_sims = cand_sims;
         a.n_cand = n_cand; a.row_item = row_item; a.n_rows = n_rows;
-        a.P = (const T*)P; a.Q = (const T*)Q; a.Bu = (const T*)bu; a.Bi = (const T*)bi;
-        a.n_items = n_items; a.k = k;
-        a.h = make_hyper<T>(mu, 0.0, 0.0, gamma, lo, hi);
         const bool ex = ex_ptr && ex_rows;
         a.ex_ptr = ex ? ex_ptr : nullptr; a.ex_rows = ex ? ex_rows : nullptr;
         a.alpha = (float)alpha; a.beta = (float)(1.0 - alpha);
@@ -291,18 +259,8 @@ extern "C" int mf_hybrid_rerank(const int32_t* query_users, int32_t n_query,
                                 float* out_scores, float* out_model, float* out_sims,
                                 int32_t* out_n_cand, void* stream) {
     (void)workspace;
-    if (dtype != MF_F32 && dtype != MF_F64) {
-        set_error("mf_hybrid_rerank: dtype=%d (must be MF_F32 or MF_F64)", dtype);
-        return MF_ERR_INVALID;
-    }
-    if (kernel < MF_LINEAR || kernel > MF_RBF) {
-        set_error("mf_hybrid_rerank: kernel=%d (must be MF_LINEAR, MF_SIGMOID or MF_RBF)", kernel);
-        return MF_ERR_INVALID;
-    }
-    if (n_factors < 0 || n_factors > kMaxFactors) {
-        set_error("mf_hybrid_rerank: n_factors=%d (must be in [0, %d])", n_factors, kMaxFactors);
-        return MF_ERR_INVALID;
-    }
+    const char* fn = "mf_hybrid_rerank";
+    if (check_model(fn, dtype, n_factors, kernel) != MF_OK) return MF_ERR_INVALID;
     if (n_query < 0) {
         set_error("mf_hybrid_rerank: n_query=%d (must be >= 0)", n_query);
         return MF_ERR_INVALID;
@@ -330,11 +288,7 @@ extern "C" int mf_hybrid_rerank(const int32_t* query_users, int32_t n_query,
     if (n_query == 0) return MF_OK;
     const void* need[] = {cand_rows, cand_sims, out_n_cand};
     const char* names[] = {"cand_rows", "cand_sims", "out_n_cand"};
-    for (int i = 0; i < 3; ++i)
-        if (!need[i]) {
-            set_error("mf_hybrid_rerank: %s is NULL", names[i]);
-            return MF_ERR_INVALID;
-        }
+    if (null_arg(fn, need, names, 3)) return MF_ERR_INVALID;
     if (amount > 0 && (!out_rows || !out_scores)) {
         set_error("mf_hybrid_rerank: %s is NULL", out_rows ? "out_scores" : "out_rows");
         return MF_ERR_INVALID;
@@ -346,11 +300,11 @@ extern "C" int mf_hybrid_rerank(const int32_t* query_users, int32_t n_query,
         return MF_ERR_INVALID;
     }
     HybridLaunch L{query_users, n_query, cand_rows, cand_sims, n_cand, row_item, n_rows,
-                   global_mean, user_biases, item_biases, user_features, item_features, n_items,
-                   n_factors, gamma, min_rating, max_rating, exclude_ptr, exclude_rows, alpha,
-                   amount, out_rows, out_scores, out_model, out_sims, out_n_cand,
-                   (hipStream_t)stream};
+                   {global_mean, user_biases, item_biases, user_features, item_features, n_items,
+                    n_factors, gamma, min_rating, max_rating},
+                   exclude_ptr, exclude_rows, alpha, amount, out_rows, out_scores, out_model,
+                   out_sims, out_n_cand, (hipStream_t)stream};
     // without a model the scores are 0 whatever the layout: one instantiation serves
     if (!user_features) return L.run<float, 16, 1, MF_LINEAR>();
-    return dispatch(dtype, n_factors, kernel, L);
+    return dispatch(fn, dtype, n_factors, kernel, L);
 }

@@ -4,8 +4,8 @@
 // top-k metric (precision / recall / NDCG / MAP / MRR at any k) and AUC is a
 // function of these ranks, so no list is selected and no score is stored.
 //
-// Pass 1 (k_rank_targets): a wave per query scores the query's targets with
-//   predict's arithmetic and writes (order key, item id) per target; a target
+// Pass 1 (k_rank_targets): a wave per query scores the query's targets
+//   (mf_score.hpp: mf_predict's value) and writes (order key, item id) per target; a target
 //   out of range or in the query's exclusion list gets the never-counted
 //   sentinel and rank -1.  out_candidates[q] starts at n_items.
 // Pass 2 (k_rank_count): workgroup (user block x, item split y).  The rows of
@@ -23,7 +23,7 @@
 //   against 10^5 scored ones per user: cheaper than a list search per score.
 #include <algorithm>
 
-#include "mf_common.hpp"
+#include "mf_score.hpp"
 #include "mf_order.hpp"
 
 namespace mf {
@@ -34,10 +34,8 @@ constexpr uint64_t kRankNoKey = ~0ull;
 
 template <typename T>
 struct RankArgs {
-    const int32_t* users; int32_t nq;
-    const T* P; const T* Q; const T* Bu; const T* Bi;
-    int32_t n_items, k, n_splits;
-    Hyper<T> h;
+    ModelView<T> m;
+    const int32_t* users; int32_t nq, n_splits;
     const int64_t* ex_ptr; const int32_t* ex_items;
     const int64_t* tg_ptr; const int32_t* tg_items;
     RankTarget* tg;
@@ -51,53 +49,17 @@ constexpr int rank_users() {
     return words >= 8 ? 2 : 16 / words;
 }
 
-// query qy's factor row in the (GS, V) lane layout; -1 (or past the end): zero row, zero bias
+// query qy's row and bias; past the last query: a zero row, a zero bias
 template <typename T, int GS, int V, int KERN>
 __device__ __forceinline__ void rank_user(const RankArgs<T>& A, int qy, int l, T (&p)[V], T& bu) {
-    const int32_t uu = qy < A.nq ? A.users[qy] : -1;
-    const bool uk = uu >= 0;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-        const int f = l + v * GS;
-        p[v] = (uk && f < A.k) ? A.P[(int64_t)uu * A.k + f] : (T)0;
-    }
-    bu = (uk && KERN != MF_RBF) ? A.Bu[uu] : (T)0;
+    load_user<T, GS, V, KERN>(A.m, qy < A.nq ? A.users[qy] : -1, l, p, bu);
 }
 
-template <typename T, int GS, int V, int KERN>
-__device__ __forceinline__ void rank_item(const RankArgs<T>& A, int64_t it, bool have, int l,
-                                          T (&q)[V], T& bi) {
-    const T* qr = A.Q + (have ? it : 0) * A.k;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-        const int f = l + v * GS;
-        q[v] = (have && f < A.k) ? qr[f] : (T)0;
-    }
-    bi = (have && KERN != MF_RBF) ? A.Bi[it] : (T)0;
-}
-
-// k_topk_scores' score (= mf_predict, bound_ratings = 0) as an order key, in every lane
-// of the group
+// the pair's score (mf_score.hpp) as mf_topk's order key, in every lane of the group
 template <typename T, int GS, int V, int KERN>
 __device__ __forceinline__ uint64_t rank_key(const Hyper<T>& h, const T (&p)[V], T bu,
                                              const T (&q)[V], T bi) {
-    T s = (T)0;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-        if constexpr (KERN == MF_RBF) {
-            const T d = p[v] - q[v];
-            s = s + d * d;
-        } else {
-            s = s + p[v] * q[v];
-        }
-    }
-    s = group_sum<GS>(s);
-    T pred;
-    if constexpr (KERN == MF_LINEAR) pred = ((h.mu + bi) + bu) + s;
-    else if constexpr (KERN == MF_SIGMOID)
-        pred = h.a + h.c * ((T)1 / ((T)1 + dexp<T>(-(((h.mu + bu) + bi) + s))));
-    else pred = h.a + h.c * dexp<T>((-h.gamma) * s);
-    return order_key((double)pred);
+    return order_key((double)score_pair<T, GS, V, KERN>(h, p, bu, q, bi));
 }
 
 // per-lane counts of one lane group -> their sum over the wave's groups (in every lane)
@@ -118,18 +80,18 @@ __global__ __launch_bounds__(kBlock) void k_rank_targets(RankArgs<T> A) {
     const int qy = (int)wq;
     T p[V], bu;
     rank_user<T, GS, V, KERN>(A, qy, l, p, bu);
-    if (lane == 0) A.out_cand[qy] = A.n_items;
+    if (lane == 0) A.out_cand[qy] = A.m.n_items;
     const int64_t t0 = A.tg_ptr[qy], t1 = A.tg_ptr[qy + 1];
     const int64_t xlo = A.ex_ptr ? A.ex_ptr[qy] : 0, xhi = A.ex_ptr ? A.ex_ptr[qy + 1] : 0;
     for (int64_t tb = t0; tb < t1; tb += R) {
         const int64_t t = tb + g;
         const bool have = t < t1;
         const int32_t it = have ? A.tg_items[t] : -1;
-        const bool ok = have && it >= 0 && it < A.n_items &&
+        const bool ok = have && it >= 0 && it < A.m.n_items &&
                         !in_sorted(A.ex_items, xlo, xhi, it);
         T q[V], bi;
-        rank_item<T, GS, V, KERN>(A, it, ok, l, q, bi);
-        const uint64_t key = rank_key<T, GS, V, KERN>(A.h, p, bu, q, bi);
+        load_item<T, GS, V, KERN>(A.m, it, ok, l, q, bi);
+        const uint64_t key = rank_key<T, GS, V, KERN>(A.m.h, p, bu, q, bi);
         if (have && l == 0) {
             RankTarget r;
             r.key = ok ? key : kRankNoKey;
@@ -149,9 +111,9 @@ __global__ __launch_bounds__(kBlock) void k_rank_count(RankArgs<T> A) {
     const int g = lane / GS, l = lane % GS;
     const int64_t q0 = (int64_t)blockIdx.x * NU;
     const int split = blockIdx.y;
-    const int64_t span = ((int64_t)A.n_items + A.n_splits - 1) / A.n_splits;
-    const int64_t ibeg = min((int64_t)A.n_items, span * split);
-    const int64_t iend = min((int64_t)A.n_items, span * (split + 1));
+    const int64_t span = ((int64_t)A.m.n_items + A.n_splits - 1) / A.n_splits;
+    const int64_t ibeg = min((int64_t)A.m.n_items, span * split);
+    const int64_t iend = min((int64_t)A.m.n_items, span * (split + 1));
     T p[NU][V], bu[NU];
     int64_t t0[NU];
     int tn[NU];
@@ -185,10 +147,10 @@ __global__ __launch_bounds__(kBlock) void k_rank_count(RankArgs<T> A) {
             const int64_t it = ib + g;
             const bool have = it < iend;
             T q[V], bi;
-            rank_item<T, GS, V, KERN>(A, it, have, l, q, bi);
+            load_item<T, GS, V, KERN>(A.m, it, have, l, q, bi);
 #pragma unroll
             for (int x = 0; x < NU; ++x) {
-                const uint64_t key = rank_key<T, GS, V, KERN>(A.h, p[x], bu[x], q, bi);
+                const uint64_t key = rank_key<T, GS, V, KERN>(A.m.h, p[x], bu[x], q, bi);
                 cnt[x] += (have && cand_before(key, (int32_t)it, tk[x], ti[x])) ? 1 : 0;
             }
         }
@@ -229,13 +191,13 @@ __global__ __launch_bounds__(kBlock) void k_rank_exclude(RankArgs<T> A) {
             const bool have = x < xhi;
             const int32_t it = have ? A.ex_items[x] : -1;
             // in range, and the first of its duplicates in the sorted list
-            const bool ok = have && it >= 0 && it < A.n_items &&
+            const bool ok = have && it >= 0 && it < A.m.n_items &&
                             (x == xlo || A.ex_items[x - 1] != it);
             nex += (ok && l == 0) ? 1 : 0;
             if (tn > 0) {                                // workgroup-uniform
                 T q[V], bi;
-                rank_item<T, GS, V, KERN>(A, it, ok, l, q, bi);
-                const uint64_t key = rank_key<T, GS, V, KERN>(A.h, p, bu, q, bi);
+                load_item<T, GS, V, KERN>(A.m, it, ok, l, q, bi);
+                const uint64_t key = rank_key<T, GS, V, KERN>(A.m.h, p, bu, q, bi);
                 cnt += (ok && cand_before(key, it, tk, ti)) ? 1 : 0;
             }
         }
@@ -258,8 +220,7 @@ static int rank_splits(int64_t user_blocks, int32_t n_items) {
 }
 
 struct RankLaunch {
-    const int32_t* users; int32_t nq; double mu; const void* bu; const void* bi;
-    const void* P; const void* Q; int32_t n_items; int32_t k; double gamma, lo, hi;
+    const int32_t* users; int32_t nq; Model m;
     const int64_t* ex_ptr; const int32_t* ex_items;
     const int64_t* tg_ptr; const int32_t* tg_items;
     void* ws; int32_t* out_rank; int32_t* out_cand;
@@ -268,19 +229,17 @@ struct RankLaunch {
     template <typename T, int GS, int V, int KERN>
     int run() {
         RankArgs<T> a;
-        a.users = users; a.nq = nq; a.P = (const T*)P; a.Q = (const T*)Q;
-        a.Bu = (const T*)bu; a.Bi = (const T*)bi; a.n_items = n_items; a.k = k;
-        a.h = make_hyper<T>(mu, 0.0, 0.0, gamma, lo, hi);
+        a.m = m.view<T>(); a.users = users; a.nq = nq;
         const bool ex = ex_ptr && ex_items;
         a.ex_ptr = ex ? ex_ptr : nullptr; a.ex_items = ex ? ex_items : nullptr;
         a.tg_ptr = tg_ptr; a.tg_items = tg_items; a.tg = (RankTarget*)ws;
         a.out_rank = out_rank; a.out_cand = out_cand;
         constexpr int NU = rank_users<T, V>();
         const int64_t ub = ((int64_t)nq + NU - 1) / NU;
-        a.n_splits = rank_splits(ub, n_items);
+        a.n_splits = rank_splits(ub, m.n_items);
         const unsigned bq = (unsigned)(((int64_t)nq + kWavesPerBlock - 1) / kWavesPerBlock);
         hipLaunchKernelGGL((k_rank_targets<T, GS, V, KERN>), dim3(bq), dim3(kBlock), 0, stream, a);
-        if (n_items > 0)
+        if (m.n_items > 0)
             hipLaunchKernelGGL((k_rank_count<T, GS, V, KERN>),
                                dim3((unsigned)ub, (unsigned)a.n_splits), dim3(kBlock), 0, stream, a);
         if (ex)
@@ -313,18 +272,7 @@ extern "C" int mf_rank(const int32_t* query_users, int32_t n_query, double globa
                        const int32_t* exclude_items, const int64_t* target_ptr,
                        const int32_t* target_items, void* workspace, int32_t* out_rank,
                        int32_t* out_candidates, void* stream) {
-    if (dtype != MF_F32 && dtype != MF_F64) {
-        set_error("mf_rank: dtype=%d (must be MF_F32 or MF_F64)", dtype);
-        return MF_ERR_INVALID;
-    }
-    if (kernel < MF_LINEAR || kernel > MF_RBF) {
-        set_error("mf_rank: kernel=%d (must be MF_LINEAR, MF_SIGMOID or MF_RBF)", kernel);
-        return MF_ERR_INVALID;
-    }
-    if (n_factors < 0 || n_factors > kMaxFactors) {
-        set_error("mf_rank: n_factors=%d (must be in [0, %d])", n_factors, kMaxFactors);
-        return MF_ERR_INVALID;
-    }
+    if (check_model("mf_rank", dtype, n_factors, kernel) != MF_OK) return MF_ERR_INVALID;
     if (n_query < 0) {
         set_error("mf_rank: n_query=%d (must be >= 0)", n_query);
         return MF_ERR_INVALID;
@@ -338,14 +286,11 @@ extern "C" int mf_rank(const int32_t* query_users, int32_t n_query, double globa
                           out_candidates};
     const char* names[] = {"query_users", "target_ptr", "target_items", "workspace", "out_rank",
                            "out_candidates"};
-    for (int i = 0; i < 6; ++i)
-        if (!need[i]) {
-            set_error("mf_rank: %s is NULL", names[i]);
-            return MF_ERR_INVALID;
-        }
-    RankLaunch L{query_users, n_query, global_mean, user_biases, item_biases, user_features,
-                 item_features, n_items, n_factors, gamma, min_rating, max_rating, exclude_ptr,
-                 exclude_items, target_ptr, target_items, workspace, out_rank, out_candidates,
-                 (hipStream_t)stream};
-    return dispatch(dtype, n_factors, kernel, L);
+    if (null_arg("mf_rank", need, names, 6)) return MF_ERR_INVALID;
+    RankLaunch L{query_users, n_query,
+                 {global_mean, user_biases, item_biases, user_features, item_features, n_items,
+                  n_factors, gamma, min_rating, max_rating},
+                 exclude_ptr, exclude_items, target_ptr, target_items, workspace, out_rank,
+                 out_candidates, (hipStream_t)stream};
+    return dispatch("mf_rank", dtype, n_factors, kernel, L);
 }

@@ -22,7 +22,7 @@
 #include <utility>
 #include <vector>
 
-#include "mf_common.hpp"
+#include "mf_score.hpp"          // predict_one
 
 namespace mf {
 
@@ -154,21 +154,6 @@ __device__ __forceinline__ SliceWave slice_wave(const SliceTab& SL) {
     s.nw = bps * kWavesPerBlock;
     s.wv = j * kWavesPerBlock + threadIdx.x / kWave;
     return s;
-}
-
-// kernels.py:21-105.  `s` = group-reduced dot product (linear/sigmoid) or
-// squared distance (rbf).
-template <typename T, int KERN>
-__device__ __forceinline__ T predict_one(T s, T bu, T bi, const Hyper<T> h) {
-    if constexpr (KERN == MF_LINEAR) {
-        return ((h.mu + bi) + bu) + s;                       // kernels.py:42-44
-    } else if constexpr (KERN == MF_SIGMOID) {
-        const T lin = ((h.mu + bu) + bi) + s;                // kernels.py:73-75
-        const T sg = (T)1 / ((T)1 + dexp<T>(-lin));          // kernels.py:17
-        return h.a + h.c * sg;                               // kernels.py:77
-    } else {
-        return h.a + h.c * dexp<T>((-h.gamma) * s);          // kernels.py:102-104
-    }
 }
 
 // rating-slot broadcast: wave-uniform source -> v_readlane, else ds_bpermute

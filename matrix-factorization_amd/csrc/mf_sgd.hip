@@ -22,18 +22,24 @@ template <typename T, int V> struct Tile {
     static constexpr int U = V >= 4 ? 1 : (V == 2 ? 2 : 4);
 };
 
+template <typename T>
+struct PredictArgs {
+    ModelView<T> m;
+    const int32_t* u; const int32_t* i;
+    int32_t bound; T* out;
+};
+
 // Batched prediction (_predict, kernel_matrix_factorization.py:448-541):
 // -1 ids read as a zero bias and an all-zero factor row (:487-499).
 template <typename T, int GS, int V, int KERN>
-__global__ __launch_bounds__(kBlock) void k_read(ReadArgs<T> A, SliceTab S) {
+__global__ __launch_bounds__(kBlock) void k_read(PredictArgs<T> A, SliceTab S) {
     constexpr int R = kWave / GS;
     constexpr int U = Tile<T, V>::U;
     constexpr int RPW = U * R;
     const int lane = threadIdx.x & (kWave - 1);
     const int g = lane / GS;
     const int l = lane % GS;
-    const int k = A.k;
-    const Hyper<T> h = A.h;
+    const Hyper<T> h = A.m.h;
     const int x_slice = blockIdx.x % S.n;
     const int64_t bps = gridDim.x / S.n;                 // blocks per slice
     const int64_t s_end = S.off[x_slice + 1];
@@ -42,7 +48,6 @@ __global__ __launch_bounds__(kBlock) void k_read(ReadArgs<T> A, SliceTab S) {
 
     for (int64_t w0 = S.off[x_slice] + wave * RPW; w0 < s_end; w0 += nwaves * RPW) {
         const int nw = (int)min((int64_t)RPW, s_end - w0);
-        int uu[U], ii[U];
         bool have[U];
         T p[U][V], q[U][V], bu[U], bi[U];
 #pragma unroll
@@ -50,39 +55,13 @@ __global__ __launch_bounds__(kBlock) void k_read(ReadArgs<T> A, SliceTab S) {
             const int idx = x * R + g;
             have[x] = idx < nw;
             const int64_t j = w0 + (have[x] ? idx : 0);
-            uu[x] = A.u[j];
-            ii[x] = A.i[j];
-            const bool uk = have[x] && uu[x] >= 0;
-            const bool ik = have[x] && ii[x] >= 0;
-            const T* pr = A.P + (int64_t)(uk ? uu[x] : 0) * k;
-            const T* qr = A.Q + (int64_t)(ik ? ii[x] : 0) * k;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const int f = l + v * GS;
-                p[x][v] = (uk && f < k) ? pr[f] : (T)0;
-                q[x][v] = (ik && f < k) ? qr[f] : (T)0;
-            }
-            if constexpr (KERN != MF_RBF) {
-                bu[x] = uk ? A.Bu[uu[x]] : (T)0;
-                bi[x] = ik ? A.Bi[ii[x]] : (T)0;
-            } else {
-                bu[x] = bi[x] = (T)0;
-            }
+            const int32_t ii = A.i[j];
+            load_user<T, GS, V, KERN>(A.m, have[x] ? A.u[j] : -1, l, p[x], bu[x]);
+            load_item<T, GS, V, KERN>(A.m, ii, have[x] && ii >= 0, l, q[x], bi[x]);
         }
 #pragma unroll
         for (int x = 0; x < U; ++x) {
-            T s = (T)0;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                if constexpr (KERN == MF_RBF) {
-                    const T d = p[x][v] - q[x][v];
-                    s = s + d * d;
-                } else {
-                    s = s + p[x][v] * q[x][v];
-                }
-            }
-            s = group_sum<GS>(s);
-            T pred = predict_one<T, KERN>(s, bu[x], bi[x], h);
+            T pred = score_pair<T, GS, V, KERN>(h, p[x], bu[x], q[x], bi[x]);
             if (have[x] && l == 0) {
                 const int64_t j = w0 + x * R + g;
                 if (A.bound) {                               // :532-536
@@ -120,21 +99,13 @@ inline int read_bps(const SliceTab& S, int rpw) {
 }
 
 struct ReadLaunch {
-    const int32_t* u; const int32_t* i; int64_t n;
-    double mu; const void* bu; const void* bi; const void* P; const void* Q;
-    int32_t k; double gamma, lo, hi; int32_t bound; void* out;
+    const int32_t* u; const int32_t* i; Model m; int32_t bound; void* out;
     hipStream_t stream; SliceTab S;
 
     template <typename T, int GS, int V, int KERN>
     int run() {
         constexpr int RPW = Tile<T, V>::U * (kWave / GS);
-        ReadArgs<T> a;
-        a.u = u; a.i = i; a.r = nullptr;
-        a.P = static_cast<const T*>(P); a.Q = static_cast<const T*>(Q);
-        a.Bu = static_cast<const T*>(bu); a.Bi = static_cast<const T*>(bi);
-        a.n = n; a.k = k; a.bound = bound; a.out = static_cast<T*>(out);
-        a.partials = nullptr;
-        a.h = make_hyper<T>(mu, 0.0, 0.0, gamma, lo, hi);
+        const PredictArgs<T> a{m.view<T>(), u, i, bound, static_cast<T*>(out)};
         const int blocks = read_bps(S, RPW) * S.n;
         hipLaunchKernelGGL((k_read<T, GS, V, KERN>), dim3(blocks), dim3(kBlock), 0,
                            stream, a, S);
@@ -834,9 +805,11 @@ extern "C" int mf_predict(const int32_t* user_ids, const int32_t* item_ids,
     if (n_pairs == 0) return MF_OK;
     SliceTab S;
     S.n = 1; S.off[0] = 0; S.off[1] = n_pairs;
-    ReadLaunch L{user_ids, item_ids, n_pairs, global_mean, user_biases,
-                 item_biases, user_features, item_features, n_factors, gamma,
-                 min_rating, max_rating, bound_ratings ? 1 : 0, out,
-                 (hipStream_t)stream, S};
-    return dispatch(dtype, n_factors, kernel, L);
+    // (n_items = 0: mf_predict is not told the item count; k_read bounds an id by >= 0 alone
+    // and must not read m.n_items)
+    ReadLaunch L{user_ids, item_ids,
+                 {global_mean, user_biases, item_biases, user_features, item_features, 0,
+                  n_factors, gamma, min_rating, max_rating},
+                 bound_ratings ? 1 : 0, out, (hipStream_t)stream, S};
+    return dispatch("mf_predict", dtype, n_factors, kernel, L);
 }

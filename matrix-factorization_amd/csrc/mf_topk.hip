@@ -19,7 +19,7 @@
 #include <climits>
 #include <cstdlib>
 
-#include "mf_common.hpp"
+#include "mf_score.hpp"
 #include "mf_order.hpp"
 
 namespace mf {
@@ -29,11 +29,8 @@ constexpr int kTopkItemsPerWave = 256;
 
 template <typename T>
 struct TopkArgs {
+    ModelView<T> m;
     const int32_t* users;
-    const T* P; const T* Q; const T* Bu; const T* Bi;
-    int32_t n_items;
-    int32_t k;
-    Hyper<T> h;
     uint64_t* keys;
 };
 
@@ -45,45 +42,18 @@ __global__ __launch_bounds__(kBlock) void k_topk_scores(TopkArgs<T> A) {
     const int qy = blockIdx.y;
     const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
     const int64_t i0 = wave * kTopkItemsPerWave;
-    if (i0 >= A.n_items) return;
-    const int k = A.k;
-    const int32_t uu = A.users[qy];
-    const bool uk = uu >= 0;
-    T p[V];
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-        const int f = l + v * GS;
-        p[v] = (uk && f < k) ? A.P[(int64_t)uu * k + f] : (T)0;
-    }
-    const T bu = (uk && KERN != MF_RBF) ? A.Bu[uu] : (T)0;
-    const int64_t iend = min((int64_t)A.n_items, i0 + kTopkItemsPerWave);
-    uint64_t* keys = A.keys + (int64_t)qy * A.n_items;
+    if (i0 >= A.m.n_items) return;
+    T p[V], bu;
+    load_user<T, GS, V, KERN>(A.m, A.users[qy], l, p, bu);
+    const int64_t iend = min((int64_t)A.m.n_items, i0 + kTopkItemsPerWave);
+    uint64_t* keys = A.keys + (int64_t)qy * A.m.n_items;
     for (int64_t ib = i0; ib < iend; ib += R) {
         const int64_t it = ib + g;
         const bool have = it < iend;
-        const T* qr = A.Q + (have ? it : 0) * k;
-        T s = (T)0;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const int f = l + v * GS;
-            const T qf = (have && f < k) ? qr[f] : (T)0;
-            if constexpr (KERN == MF_RBF) {
-                const T d = p[v] - qf;
-                s = s + d * d;
-            } else {
-                s = s + p[v] * qf;
-            }
-        }
-        s = group_sum<GS>(s);
-        if (have && l == 0) {
-            const T bi = (KERN != MF_RBF) ? A.Bi[it] : (T)0;
-            T pred;
-            if constexpr (KERN == MF_LINEAR) pred = ((A.h.mu + bi) + bu) + s;
-            else if constexpr (KERN == MF_SIGMOID)
-                pred = A.h.a + A.h.c * ((T)1 / ((T)1 + dexp<T>(-(((A.h.mu + bu) + bi) + s))));
-            else pred = A.h.a + A.h.c * dexp<T>((-A.h.gamma) * s);
-            keys[it] = order_key((double)pred);
-        }
+        T q[V], bi;
+        load_item<T, GS, V, KERN>(A.m, it, have, l, q, bi);
+        const T pred = score_pair<T, GS, V, KERN>(A.m.h, p, bu, q, bi);
+        if (have && l == 0) keys[it] = order_key((double)pred);
     }
 }
 
@@ -225,8 +195,13 @@ __global__ __launch_bounds__(kBlock) void k_topk_select(const uint64_t* __restri
 }
 
 // ---------------------------------------------------------------- fused
-// k_topk_fused: the same scores (k_read's arithmetic: lane partials of the
-// scalar layout, group_sum<GS>, predict_one) without materialising them.
+// k_topk_fused: the same scores without materialising them.  Of mf_score.hpp
+// it calls predict_one alone and keeps its own row loads, partial loop and
+// loose FusedArgs fields (what load_user / load_item / score_pair do, written
+// where it was): with GS = 64 its 16-user inner loop is wave-uniform and sits
+// at the 106-SGPR limit, and through the helpers or with a ModelView member
+// k_topk_fused<float, *, 1, MF_LINEAR> spilled 20 SGPRs for 14 / 14 / 17 and
+// ran 1.25 % slower (profiles/score_share/README.md).
 // Workgroup (split x, user block y) scores items [ibeg, iend) of its split
 // against kFusedUsers users whose rows sit in registers; every wave walks
 // one item at a time.  A score enters the user's LDS candidate list only if
@@ -319,11 +294,7 @@ __global__ __launch_bounds__(kBlock) void k_topk_fused(FusedArgs<T> A) {
                     }
                 }
                 sc = group_sum<GS>(sc);
-                T pred;                                  // predict_one (mf_rows.hpp)
-                if constexpr (KERN == MF_LINEAR) pred = ((A.h.mu + bi) + bu[x]) + sc;
-                else if constexpr (KERN == MF_SIGMOID)
-                    pred = A.h.a + A.h.c * ((T)1 / ((T)1 + dexp<T>(-(((A.h.mu + bu[x]) + bi) + sc))));
-                else pred = A.h.a + A.h.c * dexp<T>((-A.h.gamma) * sc);
+                const T pred = predict_one<T, KERN>(sc, bu[x], bi, A.h);
                 const uint64_t key = order_key((double)pred);
                 const int qy = q0 + x;
                 if (have && l == 0 && qy < A.nq && cand_before(key, it, tk[x], ti[x]) &&
@@ -437,23 +408,22 @@ inline void topk_from_keys(uint64_t* keys, int32_t nq, int32_t n_items, const in
 }
 
 struct TopkLaunch {
-    const int32_t* users; int32_t nq; double mu; const void* bu; const void* bi;
-    const void* P; const void* Q; int32_t n_items; int32_t k; double gamma, lo, hi;
+    const int32_t* users; int32_t nq; Model m;
     const int64_t* ex_ptr; const int32_t* ex_items; int32_t amount; void* ws; int32_t* out_items; void* out_scores;
     hipStream_t stream;
 
     template <typename T, int GS, int V, int KERN>
     int run() {
+        const int32_t n_items = m.n_items;
         if (topk_fused(amount)) {
             FusedArgs<T> f;
-            f.users = users; f.nq = nq; f.P = (const T*)P; f.Q = (const T*)Q;
-            f.Bu = (const T*)bu; f.Bi = (const T*)bi; f.n_items = n_items; f.k = k;
-            f.amount = amount;
+            const ModelView<T> v = m.view<T>();
+            f.users = users; f.nq = nq; f.P = v.P; f.Q = v.Q; f.Bu = v.Bu; f.Bi = v.Bi;
+            f.n_items = n_items; f.k = v.k; f.h = v.h; f.amount = amount;
             int a2 = 1;
             while (a2 < amount) a2 <<= 1;
             f.a2 = a2;
             f.n_splits = topk_splits(nq, n_items, amount);
-            f.h = make_hyper<T>(mu, 0.0, 0.0, gamma, lo, hi);
             f.ex_ptr = ex_items ? ex_ptr : nullptr; f.ex_items = ex_items;
             const size_t np = (size_t)nq * f.n_splits * amount;
             f.part_key = (uint64_t*)ws;
@@ -467,11 +437,7 @@ struct TopkLaunch {
             MF_HIP_CHECK(hipGetLastError());
             return MF_OK;
         }
-        TopkArgs<T> a;
-        a.users = users; a.P = (const T*)P; a.Q = (const T*)Q;
-        a.Bu = (const T*)bu; a.Bi = (const T*)bi;
-        a.n_items = n_items; a.k = k; a.h = make_hyper<T>(mu, 0.0, 0.0, gamma, lo, hi);
-        a.keys = (uint64_t*)ws;
+        const TopkArgs<T> a{m.view<T>(), users, (uint64_t*)ws};
         const int64_t waves = ((int64_t)n_items + kTopkItemsPerWave - 1) / kTopkItemsPerWave;
         const unsigned bx = (unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
         hipLaunchKernelGGL((k_topk_scores<T, GS, V, KERN>), dim3(bx, (unsigned)nq),
@@ -527,8 +493,10 @@ extern "C" int mf_topk(const int32_t* query_users, int32_t n_query, double globa
         set_error("mf_topk: n_items == 0");
         return MF_ERR_INVALID;
     }
-    TopkLaunch L{query_users, n_query, global_mean, user_biases, item_biases, user_features,
-                 item_features, n_items, n_factors, gamma, min_rating, max_rating, exclude_ptr,
-                 exclude_items, amount, workspace, out_items, out_scores, (hipStream_t)stream};
-    return dispatch(dtype, n_factors, kernel, L);
+    TopkLaunch L{query_users, n_query,
+                 {global_mean, user_biases, item_biases, user_features, item_features, n_items,
+                  n_factors, gamma, min_rating, max_rating},
+                 exclude_ptr, exclude_items, amount, workspace, out_items, out_scores,
+                 (hipStream_t)stream};
+    return dispatch("mf_topk", dtype, n_factors, kernel, L);
 }

@@ -14,7 +14,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "mf_common.hpp"
+#include "mf_score.hpp"
 #include "mf_order.hpp"
 
 namespace mf {
@@ -34,7 +34,7 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 //   + the rounding of the three bias additions,
 // doubled for safety.  Every item whose exact score could reach the exact
 // top `amount` stays in the list; k_topk_mm_merge rescores the survivors
-// with k_read's arithmetic (scalar layout, group_sum<GS>) and ranks them by
+// with score_pair (mf_score.hpp: mf_predict's value) and ranks them by
 // (exact score desc, item id asc).  A list whose band outgrows its capacity
 // sets *overflow: the results are then not guaranteed and the caller runs
 // the exact path (mf_topk).
@@ -60,6 +60,14 @@ struct MmArgs {
     int32_t* big;                        // users left to k_topk_mm_merge by k_topk_mm_merge_wave
     int32_t* n_big;                      // ... their count (null big: k_topk_mm_merge takes all)
 };
+
+// the model of the merges' exact rescoring: the float, MF_LINEAR, V = 1 instance
+// of mf_score.hpp, which reads no other field of h than mu
+__device__ __forceinline__ ModelView<float> mm_model(const MmArgs& A) {
+    ModelView<float> M{A.P, A.Q, A.Bu, A.Bi, A.n_items, A.k, {}};
+    M.h.mu = A.mu;
+    return M;
+}
 
 // k_topk_mm_stats: max item-row norm and max |b_i| into stats[0..1], max
 // query-user row norm into stats[2].  Each wave reads 64-row chunks; where
@@ -1156,7 +1164,7 @@ __global__ __launch_bounds__(kBlock) void k_topk_mw(MmArgs A) {
 }
 
 // per user: merge the splits' bands, keep s' >= (amount-th best s') - 2M,
-// rescore those with k_read's arithmetic, rank by (score desc, id asc) --
+// rescore those with score_pair (mf_score.hpp), rank by (score desc, id asc) --
 // the order keys and the sort of k_topk_merge, so the output is its output
 template <int GS>
 __global__ __launch_bounds__(kBlock) void k_topk_mm_merge(MmArgs A, int32_t* out_items,
@@ -1207,21 +1215,18 @@ __global__ __launch_bounds__(kBlock) void k_topk_mm_merge(MmArgs A, int32_t* out
     }
     __syncthreads();
     const int keep = s_keep;
-    // exact rescoring: one candidate per group of GS lanes (scalar layout,
-    // lane partial 0 + p_f q_f, group_sum<GS>, predict_one's additions)
-    const int32_t uu = A.users[qy];
-    const float bu = uu >= 0 ? A.Bu[uu] : 0.f;
-    const int k = A.k;
+    // exact rescoring (mf_score.hpp): one candidate per group of GS lanes
+    const ModelView<float> M = mm_model(A);
     const int g = lane / GS, l = lane % GS;
     constexpr int R = kWave / GS;
-    const float pl = (uu >= 0 && l < k) ? A.P[(int64_t)uu * k + l] : 0.f;
+    float pl[1], bu;
+    load_user<float, GS, 1, MF_LINEAR>(M, A.users[qy], l, pl, bu);
     for (int y0 = wv * R; y0 < keep; y0 += kWavesPerBlock * R) {
         const int y = y0 + g;
         const bool have = y < keep;
-        const int32_t it = have ? s_id[y] : 0;
-        const float ql = (have && l < k) ? A.Q[(int64_t)it * k + l] : 0.f;
-        const float sc = group_sum<GS>(0.f + pl * ql);
-        const float pred = ((A.mu + (have ? A.Bi[it] : 0.f)) + bu) + sc;
+        float ql[1], bi;
+        load_item<float, GS, 1, MF_LINEAR>(M, have ? s_id[y] : 0, have, l, ql, bi);
+        const float pred = score_pair<float, GS, 1, MF_LINEAR>(M.h, pl, bu, ql, bi);
         if (have && l == 0) s_key[y] = order_key((double)pred);
     }
     __syncthreads();
@@ -1292,29 +1297,25 @@ __global__ __launch_bounds__(kBlock) void k_topk_mm_merge_wave(MmArgs A, int32_t
                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)keep, 0u));
     if ((keep >> lane) & 1) s_kid[wv][pos] = id;
     asm volatile("" ::: "memory");
-    // exact rescoring, R candidates per pass (k_topk_mm_merge's arithmetic)
-    const int32_t uu = A.users[qy];
-    const float bu = uu >= 0 ? A.Bu[uu] : 0.f;
-    const int k = A.k;
+    // exact rescoring (mf_score.hpp), R candidates per pass
+    const ModelView<float> M = mm_model(A);
     const int g = lane / GS, l = lane % GS;
     constexpr int R = kWave / GS;
-    const float pl = (uu >= 0 && l < k) ? A.P[(int64_t)uu * k + l] : 0.f;
+    float pl[1], bu;
+    load_user<float, GS, 1, MF_LINEAR>(M, A.users[qy], l, pl, bu);
     constexpr int U = 4;                                 // candidates' loads in flight
     for (int y0 = 0; y0 < K; y0 += U * R) {              // wave-uniform
-        float ql[U], bq[U];
+        float ql[U][1], bq[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int y = y0 + u * R + g;
             const bool have = y < K;
-            const int32_t it = have ? s_kid[wv][y] : 0;
-            ql[u] = (have && l < k) ? A.Q[(int64_t)it * k + l] : 0.f;
-            bq[u] = have ? A.Bi[it] : 0.f;
+            load_item<float, GS, 1, MF_LINEAR>(M, have ? s_kid[wv][y] : 0, have, l, ql[u], bq[u]);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int y = y0 + u * R + g;
-            const float s2 = group_sum<GS>(0.f + pl * ql[u]);
-            const float pred = ((A.mu + bq[u]) + bu) + s2;
+            const float pred = score_pair<float, GS, 1, MF_LINEAR>(M.h, pl, bu, ql[u], bq[u]);
             if (y < K && l == 0) s_kkey[wv][y] = order_key((double)pred);
         }
     }

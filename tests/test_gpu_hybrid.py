@@ -163,7 +163,7 @@ def test_kernel_matches_the_restatement_at_every_list_length(n_cand):
 
 
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
-@pytest.mark.parametrize("k", [5, 32, 64, 100, 520])
+@pytest.mark.parametrize("k", [5, 32, 64, 100, 200, 300, 520])
 def test_kernel_matches_the_restatement_in_every_row_layout(k, dtype):
     run_config(k, dtype, "linear", 200, 150, k != 100, [10, 200])
 
@@ -171,7 +171,8 @@ def test_kernel_matches_the_restatement_in_every_row_layout(k, dtype):
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
 @pytest.mark.parametrize("kernel", ["sigmoid", "rbf"])
 def test_kernel_matches_the_restatement_for_the_other_kernels(kernel, dtype):
-    run_config(32, dtype, kernel, 65, 150, True, [10, 65])
+    for k in (32, 100):                                  # V = 1 and V = 2
+        run_config(k, dtype, kernel, 65, 150, True, [10, 65])
 
 
 def test_without_a_model_the_order_is_the_similarities():

@@ -521,11 +521,12 @@ def test_predict_topk_rank(mf, dtype, k, kernel):
     users = _read_users()
     scores = _all_scores(eng, users)
     eng.topk_mfma = False                        # the exact path
-    ids, sc = eng.topk(users, 10)
-    for q in range(len(users)):
-        order = np.argsort(~rr.order_key(scores[q]), kind="stable")[:10]
-        assert ids[q].tolist() == order.tolist(), f"user slot {q}"
-        assert np.array_equal(sc[q], scores[q][order]), f"user slot {q}"
+    for amount in (10, 65):                      # fused; above kFusedMaxAmount = 64: two-stage
+        ids, sc = eng.topk(users, amount)
+        for q in range(len(users)):
+            order = np.argsort(~rr.order_key(scores[q]), kind="stable")[:amount]
+            assert ids[q].tolist() == order.tolist(), f"amount {amount}, user slot {q}"
+            assert np.array_equal(sc[q], scores[q][order]), f"amount {amount}, user slot {q}"
     tp = np.arange(len(users) + 1, dtype=np.int64) * 3
     ti = rs.randint(0, READ_NI, 3 * len(users)).astype(np.int32)
     ti[:4] = [3, 5, 70, 149]                     # the tied pairs
