@@ -30,6 +30,9 @@
 // Per update the HBM traffic is the user row read + write (2 * 4k B at FP32)
 // and the triple; the item slab (2 * n_items * 4k B per stratum) and the
 // bias slices amortise over the block's ratings.
+//
+// Shared by both loops of k_sgd_strata_epoch: strata_wait_released, the
+// bounded wait for a user range's previous holder.
 #pragma once
 
 #include <type_traits>
@@ -597,6 +600,27 @@ __global__ __launch_bounds__(NW * kWave) void k_sgd_strata(StrataArgs<T> A) {
 // error flag is set and the workgroup leaves, so the grid always drains).
 constexpr int64_t kStrataSpinLimit = (int64_t)1 << 24;
 
+// The bounded wait of k_sgd_strata_epoch for a user range's previous holder,
+// called by thread 0: until that workgroup's counter `flag` reaches `target`.
+// Returns the abort flag (this wait gave up, or another had: the error word).
+__device__ __forceinline__ int strata_wait_released(const int32_t* flag, int target, int32_t* err) {
+    int ab = 0;
+    int64_t spins = 0;
+    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+        __builtin_amdgcn_s_sleep(2);
+        if (++spins > kStrataSpinLimit ||
+            __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+            __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ab = 1;
+            break;
+        }
+    }
+    // every load of handed-off bytes after the wait is sc1: no L1 invalidate,
+    // only keep the compiler from hoisting them above the poll
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return ab;
+}
+
 // The stratum order of one persistent launch travels in the kernel arguments
 // (no host-to-device copy per launch): C*B strata of B <= 256 workgroups (one
 // per CU) and C <= MF_STRATA_MAX_CLASSES, 16-bit entries (2 KiB).
@@ -732,20 +756,7 @@ __global__ __launch_bounds__(NW * kWave) void k_sgd_strata_epoch(StrataArgs<T> A
                 if (t >= C) {
                     // the user range's previous holder: same class, C positions back
                     const int wd = (w + s / C - (int)seq.s[t - C] / C + 2 * B) % B;
-                    int64_t spins = 0;
-                    while (__hip_atomic_load(done + wd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
-                           base + t - C + 1) {
-                        __builtin_amdgcn_s_sleep(2);
-                        if (++spins > kStrataSpinLimit ||
-                            __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                            __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            ab = 1;
-                            break;
-                        }
-                    }
-                    // every load of handed-off bytes below is sc1: no L1 invalidate,
-                    // only keep the compiler from hoisting them above the poll
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    ab = strata_wait_released(done + wd, base + t - C + 1, err);
                 }
                 s_abort = ab;
             }
@@ -812,20 +823,7 @@ __global__ __launch_bounds__(NW * kWave) void k_sgd_strata_epoch(StrataArgs<T> A
                     int ab = 0;
                     if (t >= C) {
                         // the user range's previous holder: same class, C positions back
-                        int64_t spins = 0;
-                        while (__hip_atomic_load(done + gc.wd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
-                               base + t - C + 1) {
-                            __builtin_amdgcn_s_sleep(2);
-                            if (++spins > kStrataSpinLimit ||
-                                __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                                __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                ab = 1;
-                                break;
-                            }
-                        }
-                        // every load of handed-off bytes below is sc1: no L1 invalidate,
-                        // only keep the compiler from hoisting them above the poll
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        ab = strata_wait_released(done + gc.wd, base + t - C + 1, err);
                     }
                     s_abort = ab;
                 }
@@ -1415,7 +1413,6 @@ inline bool strata_coresident(const void* kfn, int B, size_t lds, int threads) {
     return (int64_t)cus * per_cu >= B;
 }
 
-// NS of the row layout (W, GS, V) that dispatch_rows picks for (k, dtype)
 // Workgroup sizes of the strata kernels: 16 waves (the default), and 8 waves
 // for plans whose blocks are bound by the item degree rather than by the slot
 // count -- half the slots per step, half the per-step VALU of a CU, about the
