@@ -12,6 +12,7 @@ from __future__ import annotations
 import numpy as np
 import pandas as pd
 
+from .device_model import DeviceModel
 from .engine import BiasALS, SGDEngine, canonical_dtype, fit_epochs
 from .recommender_base import RecommenderBase
 
@@ -88,10 +89,9 @@ class BaselineModel(RecommenderBase):
         X = self._preprocess_data(X=X, type="predict")
         u = X["user_id"].to_numpy(np.int32)
         i = X["item_id"].to_numpy(np.int32)
-        eng = SGDEngine(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0),
-                        len(self.user_biases), len(self.item_biases), 0, "bias",
-                        self.dtype, self.device, min_rating=self.min_rating,
-                        max_rating=self.max_rating, global_mean=self.global_mean)
+        eng = DeviceModel(len(self.user_biases), len(self.item_biases), 0, "bias",
+                          self.dtype, self.device, min_rating=self.min_rating,
+                          max_rating=self.max_rating, global_mean=self.global_mean)
         eng.load_params(bu=self.user_biases, bi=self.item_biases)
         pred = eng.predict(u, i, bound_ratings)
         self.predictions_possible = ((u != -1) & (i != -1)).tolist()

@@ -72,7 +72,7 @@ import torch
 
 from . import _lib
 from .collaborative_filtering import _UserQueries, _warn_if_no_device
-from .engine import SGDEngine, _VOID, _tp, resolve_device
+from .device_model import DeviceModel, _VOID, _tp, resolve_device
 from .neighbours import DEFAULT_MAX_SIMILARITY_BYTES, NeighbourEngine, check_similarity_bytes
 from .ranking import RankingMixin
 from .recommender_base import RecommenderBase
@@ -197,9 +197,9 @@ class ContentBasedRecommender(RankingMixin, RecommenderBase):
             S = self._S_dev = eng.similarity(eng.normalize(eng.F))
         return S
 
-    def _cosine_engine(self) -> SGDEngine:
-        """A prediction-only factor engine whose rows are the normalised
-        profiles and feature rows: empty triples plus load_params."""
+    def _cosine_engine(self) -> DeviceModel:
+        """A factor model whose rows are the normalised profiles and feature
+        rows."""
         eng = self.__dict__.get("_cosine")
         if eng is None:
             ce = self._content_engine()
@@ -207,10 +207,9 @@ class ContentBasedRecommender(RankingMixin, RecommenderBase):
             with torch.cuda.device(ce.dev):
                 P = torch.from_numpy(np.ascontiguousarray(self._profiles)).to(ce.dev)
                 Pn, Qn = ce.normalize(P, dpad), ce.normalize(ce.F, dpad)
-            eng = SGDEngine(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0),
-                            self.n_users, self.n_items, dpad, "linear", "float32", self.device,
-                            min_rating=self.min_rating, max_rating=self.max_rating,
-                            global_mean=0.0)
+            eng = DeviceModel(self.n_users, self.n_items, dpad, "linear", "float32", self.device,
+                              min_rating=self.min_rating, max_rating=self.max_rating,
+                              global_mean=0.0)
             eng.load_params(Pn, Qn, np.zeros(self.n_users), np.zeros(self.n_items))
             self._cosine = eng
         return eng

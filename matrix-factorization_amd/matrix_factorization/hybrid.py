@@ -16,11 +16,11 @@ Per user, with E the float32 item-embedding rows ("the index"):
    in float32 (:72-79, :151-152).
 
 Steps 1 and 2 run through the kernels ContentBasedRecommender's cosine scoring
-uses (mf_content_profiles, mf_content_normalize, mf_topk on a prediction-only
-engine whose rows are the profiles and the index); steps 3 to 5 are one pass of
+uses (mf_content_profiles, mf_content_normalize, mf_topk on a DeviceModel
+whose rows are the profiles and the index); steps 3 to 5 are one pass of
 mf_hybrid_rerank, a workgroup per user.  Candidates and similarities stay on
 the device between the two stages; the model's parameters are read through its
-own prediction engine and are not copied.
+own predictor (``_model_args``) and are not copied.
 
 Three deliberate departures from the reference:
 
@@ -44,7 +44,7 @@ import torch
 from . import _lib
 from .collaborative_filtering import _warn_if_no_device
 from .content_based import ContentBasedRecommender, ContentEngine
-from .engine import SGDEngine, _VOID, _tp, resolve_device
+from .device_model import DeviceModel, _VOID, _tp, resolve_device
 from .utils import ranking_metrics_from_ranks
 
 MAX_CANDIDATES = 2048                  # mf_topk's largest amount
@@ -220,9 +220,8 @@ class HybridRecommender:
         return self
 
     # ---------------------------------------------------------- engines
-    def _retrieval_engine(self) -> SGDEngine:
-        """A prediction-only factor engine whose rows are the profiles and the
-        index rows (ContentBasedRecommender._cosine_engine's pattern): its
+    def _retrieval_engine(self) -> DeviceModel:
+        """A factor model whose rows are the profiles and the index rows: its
         mf_topk is the retrieval."""
         eng = self.__dict__.get("_engine")
         if eng is None:
@@ -231,15 +230,14 @@ class HybridRecommender:
             dpad = (d + 3) // 4 * 4
             pad = lambda a: np.ascontiguousarray(  # noqa: E731
                 np.pad(a, ((0, 0), (0, dpad - d))), np.float32)
-            eng = SGDEngine(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0),
-                            n_users, n_rows, dpad, "linear", "float32", self.device,
-                            min_rating=0.0, max_rating=1.0, global_mean=0.0)
+            eng = DeviceModel(n_users, n_rows, dpad, "linear", "float32", self.device,
+                              min_rating=0.0, max_rating=1.0, global_mean=0.0)
             eng.load_params(pad(self._profiles), pad(self._E), np.zeros(n_users),
                             np.zeros(n_rows))
             self._engine = eng
         return eng
 
-    def _model_side(self, eng: SGDEngine, labels: np.ndarray):
+    def _model_side(self, eng: DeviceModel, labels: np.ndarray):
         """(model engine, device int32 model user ids of ``labels``, device
         int32 model item id per index row); (None, None, None) without a model."""
         m = self.model
@@ -297,9 +295,7 @@ class HybridRecommender:
                 q1 = min(nq, q0 + chunk)
                 model = ((None, 0.0, None, None, None, None, 0, 0, _lib.MF_LINEAR, _lib.MF_F32,
                           0.0, 0.0, 0.0) if me is None else
-                         (off(d_uid, q0), me.global_mean, _tp(me.bu), _tp(me.bi), _tp(me.P),
-                          _tp(me.Q), me.n_items, me.k, me.kcode, me.dcode, me.gamma,
-                          me.min_rating, me.max_rating))
+                         (off(d_uid, q0), *me._model_args()))
                 # exclusion offsets stay absolute: the chunk's ptr array starts at row q0
                 _lib.call("mf_hybrid_rerank", model[0], q1 - q0, off(q["items"], n_cand * q0),
                           off(q["scores"], n_cand * q0), n_cand,

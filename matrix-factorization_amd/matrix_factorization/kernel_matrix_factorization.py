@@ -69,6 +69,7 @@ import numpy as np
 import pandas as pd
 
 from . import _lib, _prep
+from .device_model import DeviceModel
 from .distributed import EXCHANGES, fit_sharded, world_info
 from .engine import (EXACT_GPU_SHUFFLE_MIN, SGDEngine, canonical_dtype, fit_epochs,
                      legacy_permutation_device, resolve_device)
@@ -249,20 +250,20 @@ class KernelMF(RankingMixin, RecommenderBase):
             return arrs, None
         return arrs, tuple(_fingerprint(a) for a in arrs)
 
-    def _predictor(self) -> SGDEngine:
-        """Engine holding the current parameters, re-uploaded whenever the
-        attribute arrays were replaced or edited since the last upload."""
+    def _predictor(self) -> DeviceModel:
+        """The model on the device with the current parameters: the training
+        engine after fit / update_users, a DeviceModel uploaded anew whenever
+        the attribute arrays were replaced or edited since the last upload."""
         eng = getattr(self, "_pred_engine", None)
         key = self._param_key()
         old = getattr(self, "_pred_key", None)
         same = (old is not None and all(a is b for a, b in zip(old[0], key[0]))
                 and old[1] == key[1])
         if eng is None or not same:
-            eng = SGDEngine(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0),
-                            len(self.user_features), len(self.item_features),
-                            self.n_factors, self.kernel, self.dtype, self.device,
-                            gamma=self.gamma, min_rating=self.min_rating,
-                            max_rating=self.max_rating, global_mean=self.global_mean)
+            eng = DeviceModel(len(self.user_features), len(self.item_features),
+                              self.n_factors, self.kernel, self.dtype, self.device,
+                              gamma=self.gamma, min_rating=self.min_rating,
+                              max_rating=self.max_rating, global_mean=self.global_mean)
             eng.load_params(self.user_features, self.item_features,
                             self.user_biases, self.item_biases)
             self._pred_engine = eng
@@ -394,7 +395,7 @@ class KernelMF(RankingMixin, RecommenderBase):
         self._sync_params(eng)
         self._pred_engine = eng
 
-    def _ranking_backend(self) -> SGDEngine:
+    def _ranking_backend(self) -> DeviceModel:
         """recommend_batch / rank_items / evaluate_topk (ranking.RankingMixin)
-        run on the predictor engine: mf_topk and mf_rank."""
+        run on the predictor: mf_topk and mf_rank."""
         return self._predictor()

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _VOID, _tp, resolve_device
+from .device_model import _VOID, _tp, exclusion_csr, resolve_device, target_csr
 
 DEFAULT_MAX_SIMILARITY_BYTES = 16 << 30      # policy, not a measurement
 PREDICT_CHUNK = 1 << 20                      # pairs per mf_cf_predict launch (<= 2^25)
@@ -215,14 +215,11 @@ class NeighbourEngine:
 
     def _exclusions(self, nq: int, ex_ptr, ex_items):
         """The exclusion CSR on the device (offsets from 0), or (None, None)."""
+        # (mf_cf_topk / mf_cf_rank take the lists in any order)
+        ex_ptr, ex_items = exclusion_csr(nq, ex_ptr, ex_items, sort=False)
         if ex_ptr is None:
             return None, None
-        ex_ptr = np.ascontiguousarray(ex_ptr, np.int64)
-        if len(ex_ptr) != nq + 1:
-            raise ValueError("ex_ptr needs n_query + 1 offsets")
-        ex_items = np.ascontiguousarray(ex_items, np.int32)[ex_ptr[0]:ex_ptr[-1]]
-        return (self._to(ex_ptr - ex_ptr[0], np.int64),
-                self._to(ex_items if len(ex_items) else np.zeros(1, np.int32), np.int32))
+        return self._to(ex_ptr, np.int64), self._to(ex_items, np.int32)
 
     def scores(self, queries: np.ndarray, side: int, n_neighbors: int,
                global_mean: float) -> np.ndarray:
@@ -274,21 +271,14 @@ class NeighbourEngine:
     def rank(self, queries: np.ndarray, side: int, n_neighbors: int, global_mean: float,
              tgt_ptr: np.ndarray, tgt_items: np.ndarray, ex_ptr=None, ex_items=None):
         """Exact rank of each target among its query's candidates (mf_cf_rank):
-        (ranks int32[n_targets], n_candidates int32[n_query]), SGDEngine.rank's
+        (ranks int32[n_targets], n_candidates int32[n_query]), DeviceModel.rank's
         contract: ``tgt_ptr`` / ``tgt_items`` are a CSR of target ids per query
         (any order, repeats allowed); a target out of range or excluded for
         its query gets rank -1."""
         nq, nt = len(queries), self.n_targets(side)
-        tgt_ptr = np.ascontiguousarray(tgt_ptr, np.int64)
-        tgt_items = np.ascontiguousarray(tgt_items, np.int32)
-        if len(tgt_ptr) != nq + 1:
-            raise ValueError("tgt_ptr needs n_query + 1 offsets")
+        tgt_ptr, tgt_items, n_tgt = target_csr(nq, tgt_ptr, tgt_items)
         if nq == 0:
             return np.zeros(0, np.int32), np.zeros(0, np.int32)
-        tgt_ptr = tgt_ptr - tgt_ptr[0]
-        n_tgt = int(tgt_ptr[-1])
-        if np.any(np.diff(tgt_ptr) < 0) or n_tgt > len(tgt_items):
-            raise ValueError("tgt_ptr must be non-decreasing and end within tgt_items")
         ranks = torch.empty(max(n_tgt, 1), dtype=torch.int32, device=self.dev)
         cands = torch.empty(nq, dtype=torch.int32, device=self.dev)
         chunk = min(nq, self._query_chunk(side))
@@ -296,7 +286,7 @@ class NeighbourEngine:
             d_q = self._to(queries, np.int32)
             d_ptr, d_ex = self._exclusions(nq, ex_ptr, ex_items)
             d_tp = self._to(tgt_ptr, np.int64)
-            d_ti = self._to(tgt_items[:n_tgt] if n_tgt else np.zeros(1, np.int32), np.int32)
+            d_ti = self._to(tgt_items if n_tgt else np.zeros(1, np.int32), np.int32)
             ws = torch.empty(max(8 * chunk * nt, 8), dtype=torch.uint8, device=self.dev)
             for q0 in range(0, nq, chunk):
                 m = min(chunk, nq - q0)

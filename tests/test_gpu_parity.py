@@ -324,7 +324,7 @@ def test_fit_empty_and_pickle(mf):
 
 
 def _topk_engine(k, nu, ni, seed, dup_items=0, zero_users=0):
-    from matrix_factorization.engine import SGDEngine
+    from matrix_factorization.device_model import DeviceModel
 
     rs = np.random.RandomState(seed)
     P = rs.normal(0, 0.3, (nu, k)).astype(np.float32)
@@ -336,9 +336,8 @@ def _topk_engine(k, nu, ni, seed, dup_items=0, zero_users=0):
         bi[:dup_items] = bi[0]
     if zero_users:                    # all-zero rows: every score is mu + b_i + b_u
         P[:zero_users] = 0.0
-    eng = SGDEngine(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0), nu, ni, k,
-                    "linear", "float32", "cuda:0", min_rating=1.0, max_rating=5.0,
-                    global_mean=3.5)
+    eng = DeviceModel(nu, ni, k, "linear", "float32", "cuda:0", min_rating=1.0, max_rating=5.0,
+                      global_mean=3.5)
     eng.load_params(P, Q, bu, bi)
     return eng
 

@@ -18,16 +18,15 @@ MF_ERR_INVALID = 1
 
 
 def make_engine(k, nu, ni, seed, kernel="linear", dtype="float32"):
-    from matrix_factorization.engine import SGDEngine
+    from matrix_factorization.device_model import DeviceModel
 
     rs = np.random.RandomState(seed)
     P = rs.normal(0, 0.3, (nu, k))
     Q = rs.normal(0, 0.3, (ni, k))
     bu = rs.normal(0, 0.1, nu)
     bi = rs.normal(0, 0.1, ni)
-    eng = SGDEngine(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0), nu, ni, k,
-                    kernel, dtype, "cuda:0", gamma=0.7, min_rating=1.0, max_rating=5.0,
-                    global_mean=3.5)
+    eng = DeviceModel(nu, ni, k, kernel, dtype, "cuda:0", gamma=0.7, min_rating=1.0,
+                      max_rating=5.0, global_mean=3.5)
     eng.load_params(P, Q, bu, bi)
     return eng, (P, Q, bu, bi)
 

@@ -462,14 +462,13 @@ READ_NU, READ_NI = 90, 150
 
 
 def _read_engine(kernel, k, dtype):
-    from matrix_factorization.engine import SGDEngine
+    from matrix_factorization.device_model import DeviceModel
 
     start = _params(READ_NU, READ_NI, k, dtype, 300 + k)
     P, Q, bu, bi = start
     Q[5], bi[5] = Q[3], bi[3]                    # an exact tie for every user
     Q[149], bi[149] = Q[70], bi[70]
-    eng = SGDEngine(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0), READ_NU,
-                    READ_NI, k, kernel, dtype, "cuda:0", global_mean=3.4, **_hyp(k))
+    eng = DeviceModel(READ_NU, READ_NI, k, kernel, dtype, "cuda:0", global_mean=3.4, **_hyp(k))
     eng.load_params(*start)
     return eng, start
 

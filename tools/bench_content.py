@@ -30,7 +30,7 @@ sys.path.insert(0, os.path.join(ROOT, "matrix-factorization_amd"))
 from bench_cf import held_out, synth, timed  # noqa: E402
 from matrix_factorization import _lib  # noqa: E402
 from matrix_factorization.content_based import ContentEngine  # noqa: E402
-from matrix_factorization.engine import SGDEngine, _tp  # noqa: E402
+from matrix_factorization.device_model import DeviceModel, _tp  # noqa: E402
 from matrix_factorization.neighbours import NeighbourEngine  # noqa: E402
 
 
@@ -97,8 +97,8 @@ def leg(name, nu, ni, nnz, skew, d, binary, n_neighbors, n_pairs, n_query, reps,
     np.clip(pm[pu], 0.5, 5.0)
     out["predict_reference_host_ms"] = (time.perf_counter() - t0) * 1e3
 
-    cos = SGDEngine(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0), nu, ni, dpad,
-                    "linear", "float32", dev, min_rating=0.5, max_rating=5.0, global_mean=0.0)
+    cos = DeviceModel(nu, ni, dpad, "linear", "float32", dev, min_rating=0.5, max_rating=5.0,
+                      global_mean=0.0)
     cos.load_params(Pn, Qn, np.zeros(nu), np.zeros(ni))
     d_u, d_i = torch.from_numpy(pu).to(dev), torch.from_numpy(pi).to(dev)
     res32 = torch.empty(n_pairs, dtype=torch.float32, device=dev)

@@ -23,7 +23,7 @@ def main():
     import torch
 
     import bench
-    from matrix_factorization.engine import SGDEngine
+    from matrix_factorization.device_model import DeviceModel
 
     nu, ni, nnz, k, _, _ = bench.WORKLOADS["topk"]
     u, i, r = bench.synth(nu, ni, nnz)
@@ -41,9 +41,8 @@ def main():
     ex_ptr = np.concatenate([[0], np.cumsum(np.bincount(qpos, minlength=n_query))]).astype(np.int64)
     bu0 = rs.normal(0, 0.1, nu)
     bi0 = rs.normal(0, 0.1, ni)
-    eng = SGDEngine(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0), nu, ni, k,
-                    "linear", "float32", torch.device("cuda", 0), min_rating=1.0,
-                    max_rating=5.0, global_mean=mu)
+    eng = DeviceModel(nu, ni, k, "linear", "float32", torch.device("cuda", 0), min_rating=1.0,
+                      max_rating=5.0, global_mean=mu)
     eng.load_params(P0, Q0, bu0, bi0)
     batch = eng.topk_prepare(users, amount, ex_ptr, ex_items)
     eng.topk_launch(batch)
